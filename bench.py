@@ -20,7 +20,7 @@ random-binary generator of the same section (p = 0.5: 98 % infeasible, the easy
 mix; p = 0.1).  All of these, the hand-down variants and the other configs are
 secondary keys of the default run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frontier B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frontier B] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -583,6 +583,40 @@ def shard(total, world, rank):
     return np.arange(rank, total, world)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, records, incumbent, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy in float64 (the int32 fields exactly,
+    `iters` with its flag bits) -- the records of this rank's nodes (obj, dual_obj, status, iters, primal, dual) and the incumbent.
+    Every entry written is finite: what a record does not define -- the objective of an infeasible node (+inf) and its primal
+    (NaN) -- is written as 0, and nonfinite.npy holds, per node, how many entries of its record were not finite (the status says
+    which nodes have no objective; a NaN anywhere else shows there too).  incumbent.npy: [value, 1] or, no incumbent yet, [0, 0].
+    Above DUMP_BYTES_MAX in all (shared by the ranks), the records of a fixed sample of nodes (RandomState(0)), whose indices go
+    to nodes.npy.  At N > 1 every rank writes its own shard, names suffixed _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.cpu().numpy().astype(np.float64) for k, v in records.items() if v is not None}
+    B = len(arrs['obj'])
+    nonfinite = np.zeros(B)
+    for k, a in arrs.items():
+        bad = ~np.isfinite(a)
+        nonfinite += bad.reshape(B, -1).sum(axis=1)
+        a[bad] = 0.
+    arrs['nonfinite'] = nonfinite
+    row_bytes = sum(a[0].nbytes for a in arrs.values()) + 8          # (+ its entry of nodes.npy)
+    keep = max(1, min(B, (DUMP_BYTES_MAX // world - (64 << 10)) // row_bytes))   # (64 kB: the .npy headers and the incumbent)
+    if keep < B:
+        nodes = np.sort(np.random.RandomState(0).choice(B, keep, replace=False))
+        arrs = {k: a[nodes] for k, a in arrs.items()}
+        arrs['nodes'] = nodes.astype(np.float64)
+    ub = float(incumbent.cpu().numpy()[0])
+    arrs['incumbent'] = np.array([ub, 1.]) if np.isfinite(ub) else np.zeros(2)
+    suffix = '_rank%d' % rank if world > 1 else ''
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + suffix + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -607,7 +641,12 @@ def main():
     ap.add_argument('--rehearse-on-one-gpu', action='store_true',
                     help='N > 1 ranks all on cuda:0 with a gloo group: rehearses the multi-rank path on a one-GPU box '
                          '(the number it prints is not a scaling measurement)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB in all): '
+                         'the records of the frontier nodes and the incumbent; the same arguments give the same inputs every run')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # Called the way the one-GPU run is called (`python bench.py --gpus N ...`): start the N ranks as a CHILD process --
@@ -684,10 +723,11 @@ def main():
             x0_h = np.array([0., 0., 1., 0.])
     fix = torch.from_numpy(fix_h).to(dev)
     x0 = torch.from_numpy(x0_h).to(dev)
-    out = dict(obj=torch.empty(B, dtype=torch.float64, device=dev), dual_obj=torch.empty(B, dtype=torch.float64, device=dev),
-               status=torch.empty(B, dtype=torch.int32, device=dev), iters=torch.empty(B, dtype=torch.int32, device=dev),
-               primal=torch.empty(B, ctrl.qp.n_primal, dtype=torch.float64, device=dev),
-               dual=torch.empty(B, ctrl.qp.n_dual, dtype=torch.float64, device=dev))
+    # (zeroed, not empty: an entry a record leaves unwritten reads the same in every run, see --dump-outputs)
+    out = dict(obj=torch.zeros(B, dtype=torch.float64, device=dev), dual_obj=torch.zeros(B, dtype=torch.float64, device=dev),
+               status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
+               primal=torch.zeros(B, ctrl.qp.n_primal, dtype=torch.float64, device=dev),
+               dual=torch.zeros(B, ctrl.qp.n_dual, dtype=torch.float64, device=dev))
     fully_fixed = torch.from_numpy((fix_h >= 0).all(axis=1)).to(dev)
     ub = torch.full((1,), float('inf'), dtype=torch.float64, device=dev)
     warm = None
@@ -736,6 +776,9 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:    # (before the strong-scaling figure below, which reuses the rows of `out`)
+        names = dump_outputs(args.dump_outputs, out, ub, rank, world)
+        progress('rank %d: outputs of the last timed step written to %s: %s' % (rank, args.dump_outputs, ', '.join(names)))
 
     # BASELINE configs[2] as written (ONE frontier of 1024 nodes over the ranks, node k to rank k mod N; strong scaling)
     # beside the weak default, in the same multi-GPU run: same step (solve the shard, all-reduce the incumbent), same

@@ -195,24 +195,23 @@ inline std::string compiler() { const char *e = getenv("HMPC_HIPCC"); return e ?
 inline std::string arch() { const char *e = getenv("HMPC_JIT_ARCH"); return e ? e : HMPC_ARCH; }
 
 // FNV-1a over everything a kernel is compiled from: the kernel sources, this file (it writes the translation unit and the
-// command line), the extra flags, the architecture and the compiler's identity (its resolved path, size and modification
-// time: another ROCm under the same path is another compiler) -- an edit or an upgrade of any of them is another cache entry
+// command line), the extra flags, the architecture and the compiler's identity (its resolved path and its contents: another
+// ROCm under the same path is another compiler; NOT its modification time, which an installation copied from an image need
+// not keep -- the names in the VALIDATED manifest must be the same wherever the same compiler is) -- an edit or an upgrade of
+// any of them is another cache entry
 inline uint64_t source_hash()
 {
     uint64_t hsh = 1469598103934665603ull;
     auto mix = [&hsh](const std::string &t) { for (char ch : t) { hsh ^= (unsigned char)ch; hsh *= 1099511628211ull; } hsh ^= 0xffu; hsh *= 1099511628211ull; };
     mix(extra_flags());
     mix(arch());
+    std::string cc = compiler();
     {
-        std::string cc = compiler();
         char real[4096];
         if (realpath(cc.c_str(), real)) cc = real;
-        struct stat st;
-        char id[96] = "";
-        if (stat(cc.c_str(), &st) == 0) snprintf(id, sizeof id, ":%lld:%lld", (long long)st.st_size, (long long)st.st_mtime);
-        mix(cc + id);
+        mix(cc);
     }
-    for (const std::string &f : {source_dir() + "/hmpc_kernel.hip", source_dir() + "/hmpc_device.h", source_dir() + "/hmpc_jit.h", include_dir() + "/hmpc.h"}) {
+    for (const std::string &f : {cc, source_dir() + "/hmpc_kernel.hip", source_dir() + "/hmpc_device.h", source_dir() + "/hmpc_jit.h", include_dir() + "/hmpc.h"}) {
         std::ifstream in(f, std::ios::binary);
         char buf[4096];
         while (in) {
