@@ -11,7 +11,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "hmpc_device.h"
@@ -34,6 +36,61 @@ static int fail(int code, const std::string &msg)
             return fail(HMPC_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
+// The one owner of device (hipMalloc) and pinned host (hipHostMalloc) memory in this library: a block of size() elements of
+// T, released with its owner.  Converts to T * wherever a raw pointer is read (DevProb, kernel arguments, copies).
+template <class T, bool Pinned>
+class Buffer {
+public:
+    Buffer() = default;
+    Buffer(Buffer &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    Buffer &operator=(Buffer &&o) noexcept
+    {
+        if (this != &o) { release(); std::swap(p_, o.p_); std::swap(n_, o.n_); }
+        return *this;
+    }
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { release(); }
+    operator T *() const { return p_; }
+    size_t size() const { return n_; }
+    void release()
+    {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // a new block of n elements in place of the old one (at least one element is allocated: a view of an empty array is not null)
+    hipError_t alloc(size_t n)
+    {
+        release();
+        void *q = nullptr;
+        const size_t bytes = (n ? n : 1) * sizeof(T);
+        const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+        if (e == hipSuccess) { p_ = (T *)q; n_ = n; }
+        return e;
+    }
+    // Room for `want` elements: a block that is short (or absent) is replaced by one of `cap` elements -- the caller's slack --
+    // once `stream` has finished with it; `keep` leading elements are copied across.
+    hipError_t grow(size_t want, size_t cap, hipStream_t stream, size_t keep = 0)
+    {
+        if (p_ && want <= n_) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return e;
+        if (!p_ || !keep) return alloc(cap);
+        Buffer next;
+        if ((e = next.alloc(cap)) != hipSuccess) return e;
+        if ((e = hipMemcpy(next.p_, p_, keep * sizeof(T), Pinned ? hipMemcpyHostToHost : hipMemcpyDeviceToDevice)) != hipSuccess) return e;
+        *this = std::move(next);
+        return hipSuccess;
+    }
+
+private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+template <class T> using DevBuf = Buffer<T, false>;
+template <class T> using PinBuf = Buffer<T, true>;
+
 struct hmpc_cfg { // the kernel used for 1 / 2 / 4 waves per node, its LDS carve and resident-node count
     hmpc_kernel_choice k{};
     size_t lds = 0;
@@ -52,44 +109,43 @@ struct hmpc_cfg { // the kernel used for 1 / 2 / 4 waves per node, its LDS carve
 
 struct hmpc_handle {
     int device = 0;
-    bool dry = false; // hmpc_jit_build_problem: the host side of hmpc_create without a device (nothing uploaded, nothing launched)
     hmpc_cfg cfg[3];
-    DevProb dp{};
-    std::vector<void *> allocs;
-    double *rows_ws = nullptr;
-    int32_t *order = nullptr; // processing order of large frontiers (hmpc_order_kernel)
-    int order_cap = 0;
-    int32_t *pend = nullptr;  // two-launch form of the lazy terminal set: [0] how many nodes wait for their second solve, [1 ..] which
-    int pend_cap = 0;
-    void *d_shift = nullptr; // staging of the host-pointer shift
-    size_t shift_staged = 0;
-    double *shift_tv = nullptr; // per tree: what the shift needs of (x0, u0) only (hmpc_shift_tree_kernel)
-    double *shift_MT2 = nullptr; // M_mu in pairs of columns, as hmpc_shift_row_kernel keeps it in LDS
-    size_t shift_tv_cap = 0;
-    double *trace = nullptr;
+    DevProb dp{};               // its pointers are views into the blocks below
+    std::vector<DevBuf<char>> blocks;       // the problem's arrays (hmpc_create)
+    std::vector<DevBuf<char>> shift_blocks; // the shift's maps (hmpc_set_shift_maps; a second call replaces them)
+    const double *shift_MT2 = nullptr;      //   M_mu in pairs of columns, as hmpc_shift_row_kernel keeps it in LDS
+    DevBuf<double> fac_ws;
+    DevBuf<int> work_counter;
+    DevBuf<double> rows_ws;
+    DevBuf<int32_t> order; // processing order of large frontiers (hmpc_order_kernel)
+    DevBuf<int32_t> pend;  // two-launch form of the lazy terminal set: [0] how many nodes wait for their second solve, [1 ..] which
+    DevBuf<char> d_shift;  // staging of the host-pointer shift
+    DevBuf<double> shift_tv; // per tree: what the shift needs of (x0, u0) only (hmpc_shift_tree_kernel)
+    DevBuf<double> trace;
     size_t lds = 0;
     int max_grid = 0, last_grid = 0;
     // staging for the host-pointer entry point
-    void *d_x0 = nullptr;    // one device block (inputs, then outputs: stage_layout)
-    void *h_stage = nullptr; // its pinned host mirror
-    int staged = 0;
-    bool staged_warm = false; // the blocks have room for one handed-down parent record per node
+    DevBuf<char> d_stage; // one device block (inputs, then outputs: stage_layout)
+    PinBuf<char> h_stage; // its pinned host mirror
     int last_cfg = -1;            // configuration (0, 1, 2: 1 / 2 / 4 waves per node) of the last launch
     // SECOND OPINION (hmpc_solve_batch_device): nodes a compiled kernel leaves undecided are listed on the device and solved again
     // by the shipped kernel in the same stream.  hard: [0] how many of them the shipped kernel leaves undecided too, [1] its work
     // counter, [2] how many the compiled kernel left, [3 ..] which.  The two counts of the last call travel to h_hard (pinned)
     // behind hard_done and are looked at when the next call comes, or when a caller that has synchronised asks (hmpc_second_opinion_review).
-    int32_t *hard = nullptr;
-    int hard_cap = 0;
-    int32_t *h_hard = nullptr;
+    DevBuf<int32_t> hard;
+    PinBuf<int32_t> h_hard;
     hipEvent_t hard_done = nullptr;
     int hard_cfg = -1;            // configuration the counts in flight belong to (-1: none)
     int second_runs = 0;          // calls in which the shipped kernel was asked (for the tests)
-    void *chk = nullptr;          // device block of the first-use check: 2 x HMPC_CHECK_NODES x (obj, dual_obj, status, iters)
-    void *h_chk = nullptr;        //   its PINNED host mirror (objectives, dual objectives, statuses of the three runs, the hand-down index)
+    DevBuf<char> chk;             // device block of the first-use check (check_layout)
+    PinBuf<char> h_chk;           //   its PINNED host mirror (objectives, dual objectives, statuses of the three runs, the hand-down index)
     int jit_rejected = 0;         //   compiled kernels dropped by it
     std::vector<void *> jit_libs; // shared objects of kernels compiled for this problem's shape (hmpc_jit.h); never unloaded
     int jit_kernels = 0;          //   how many of the three wave counts run on such a kernel (hmpc_kernel_info)
+    hmpc_handle() = default;
+    hmpc_handle(const hmpc_handle &) = delete;
+    hmpc_handle &operator=(const hmpc_handle &) = delete;
+    ~hmpc_handle() { if (hard_done) (void)hipEventDestroy(hard_done); }
 };
 
 namespace {
@@ -151,36 +207,29 @@ void build_stage(const hmpc_problem &q, const double *F, const double *G, const 
         }
 }
 
-template <class T>
-int upload(hmpc_handle *h, const std::vector<T> &v, const T **out)
-{
-    void *d = nullptr;
-    if (h->dry) { *out = nullptr; return HMPC_OK; }
-    const size_t bytes = (v.size() ? v.size() : 1) * sizeof(T);
-    HIPCHK(hipMalloc(&d, bytes));
-    h->allocs.push_back(d);
-    if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T *>(d);
-    return HMPC_OK;
-}
+// Host arrays into blocks a handle owns, DevProb's pointers set to them.  After the first failure nothing more is uploaded:
+// rc and hmpc_last_error hold that failure.
+struct Uploader {
+    std::vector<DevBuf<char>> &blocks;
+    int rc = HMPC_OK;
+    template <class T> void operator()(const std::vector<T> &v, const T *&view) { if (rc == HMPC_OK) rc = put(v, view); }
+    template <class T> int put(const std::vector<T> &v, const T *&view)
+    {
+        DevBuf<char> d;
+        HIPCHK(d.alloc((v.size() ? v.size() : 1) * sizeof(T)));
+        if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        view = (const T *)static_cast<char *>(d);
+        blocks.push_back(std::move(d));
+        return HMPC_OK;
+    }
+};
 
-int upload_stage(hmpc_handle *h, const StageHost &s, SparseStage &d)
+void upload_stage(Uploader &up, const StageHost &s, SparseStage &d)
 {
-    d.m = s.m;
-    d.mg = s.mg;
-    int rc;
-    if ((rc = upload(h, s.rptr, &d.rptr))) return rc;
-    if ((rc = upload(h, s.rcol, &d.rcol))) return rc;
-    if ((rc = upload(h, s.rval, &d.rval))) return rc;
-    if ((rc = upload(h, s.cptr, &d.cptr))) return rc;
-    if ((rc = upload(h, s.crow, &d.crow))) return rc;
-    if ((rc = upload(h, s.cval, &d.cval))) return rc;
-    if ((rc = upload(h, s.gptr, &d.gptr))) return rc;
-    if ((rc = upload(h, s.grow, &d.grow))) return rc;
-    if ((rc = upload(h, s.gval, &d.gval))) return rc;
-    if ((rc = upload(h, s.h, &d.h))) return rc;
-    if ((rc = upload(h, s.scale, &d.scale))) return rc;
-    return HMPC_OK;
+    up(s.rptr, d.rptr); up(s.rcol, d.rcol); up(s.rval, d.rval);
+    up(s.cptr, d.cptr); up(s.crow, d.crow); up(s.cval, d.cval);
+    up(s.gptr, d.gptr); up(s.grow, d.grow); up(s.gval, d.gval);
+    up(s.h, d.h); up(s.scale, d.scale);
 }
 
 // Wave counts for which this problem gets a register kernel compiled with its sizes (hmpc_jit_prepare_sized): placeholders
@@ -330,39 +379,77 @@ static void hmpc_install_backtrace()
     (void)once;
 }
 
-// hmpc_create; with `built` the DRY form behind hmpc_jit_build_problem: the same host code up to the choice of kernels --
-// which compiles what this problem's kernels need into the cache -- without a device: nothing is uploaded, no handle returned.
-static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_handle **out, std::vector<std::string> *built)
+namespace {
+
+constexpr size_t LDS_PER_CU = 160 * 1024;
+
+// The host side of a problem (step (a) of hmpc_create): DevProb's sizes and options -- its pointers stay null -- and every array
+// the kernels read except the caller's own, which setup_device uploads as they are.
+struct HostProblem {
+    DevProb p{};
+    StageHost reg; // the stage rows; Gram lists in the order of ei / ej
+    std::vector<double> ccv, Ct, ht, sct, P, PT, Cdn, sval;
+    std::vector<int> cci, ei, ej, drow, rinfo, sptr, srow, nrow;
+};
+
+// dense / singleton split of the stage rows (generic kernel)
+void split_rows(HostProblem &hp)
 {
-    g_err.clear();
-    const bool dry = built != nullptr;
-    if (!q || (!out && !dry)) return fail(HMPC_EINVAL, "null problem or output pointer");
-    if (q->nx < 1 || q->nu < 1 || q->nub < 0 || q->nub > q->nu || q->T < 2 || q->nc < 0 || q->ncT < q->nc ||
-        q->nq < 0 || q->nr < 0 || q->nqT < 0)
-        return fail(HMPC_EINVAL, "inconsistent sizes (need nx,nu >= 1, 0 <= nub <= nu, T >= 2, ncT >= nc)");
-    if (!q->A || !q->B || !q->F || !q->G || !q->h || !q->F_Tm1 || !q->G_Tm1 || !q->h_Tm1 || !q->Q || !q->R || !q->Q_T)
-        return fail(HMPC_EINVAL, "null matrix pointer");
-
-    hmpc_handle *h = new hmpc_handle();
-    h->dry = dry;
-    int dev = opt ? opt->device : -1;
-    if (!dry) {
-        if (dev < 0) {
-            if (hipGetDevice(&dev) != hipSuccess) { delete h; return fail(HMPC_EDEVICE, "no HIP device available"); }
-        }
-        h->device = dev;
-        if (hipSetDevice(dev) != hipSuccess) { delete h; return fail(HMPC_EDEVICE, "hipSetDevice failed"); }
+    DevProb &p = hp.p;
+    const int nz = p.nz;
+    const std::vector<double> &C = hp.reg.C;
+    std::vector<int> &drow = hp.drow, &rinfo = hp.rinfo, &sptr = hp.sptr, &srow = hp.srow, &nrow = hp.nrow;
+    std::vector<double> &sval = hp.sval, &Cdn = hp.Cdn;
+    rinfo.assign(p.mreg, 0);
+    sptr.assign(nz + 1, 0);
+    sval.assign(p.mreg, 0.0);
+    for (int r = 0; r < p.mreg; r++) {
+        int cnt = 0, col = 0;
+        for (int j = 0; j < nz; j++)
+            if (C[(size_t)r * nz + j] != 0.0) { cnt++; col = j; }
+        if (cnt >= 2) { rinfo[r] = -((int)drow.size() + 1); drow.push_back(r); }
+        else { rinfo[r] = col; sval[r] = C[(size_t)r * nz + col]; }
     }
+    p.nd = (int)drow.size();
+    p.ndp = (p.nd + 3) / 4 * 4;
+    Cdn.assign((size_t)p.ndp * nz, 0.0);
+    for (int k = 0; k < p.nd; k++)
+        for (int j = 0; j < nz; j++) Cdn[(size_t)k * nz + j] = C[(size_t)drow[k] * nz + j];
+    drow.resize(p.ndp, 0);
+    for (int j = 0; j < nz; j++) {
+        for (int r = 0; r < p.mreg; r++)
+            if (rinfo[r] == j && sval[r] != 0.0) srow.push_back(r);
+        sptr[j + 1] = (int)srow.size();
+    }
+    p.ns = (int)srow.size();
+    for (int r = 0; r < p.mreg; r++)
+        if (rinfo[r] >= 0) nrow.push_back(r);
+    p.nd_magic = p.nd > 0 ? (unsigned)((0x100000000ULL + p.nd - 1) / p.nd) : 0u;
+    p.nn_magic = !nrow.empty() ? (unsigned)((0x100000000ULL + nrow.size() - 1) / nrow.size()) : 0u;
+    if (nrow.empty()) nrow.push_back(0);
+    if (Cdn.empty()) Cdn.push_back(0.0);
+    if (drow.empty()) drow.push_back(0);
+    if (srow.empty()) srow.push_back(0);
+}
 
-    DevProb &p = h->dp;
-    const int nx = q->nx, nu = q->nu, nz = q->nx + q->nu;
-    p.nx = q->nx; p.nu = q->nu; p.nub = q->nub; p.nuc = q->nu - q->nub; p.nz = q->nx + q->nu; p.T = q->T;
-    p.nc = q->nc; p.ncL = q->ncT; p.nT = q->ncT - q->nc; p.mreg = q->nc + 2 * q->nub;
-    p.Toff = q->T * p.mreg; p.M = p.Toff + p.nT; p.Mpad = (p.M + 255) / 256 * 256;
-    p.n = q->T * p.nz + q->nx; p.ne = p.nz * (p.nz + 1) / 2;
-    p.nq = q->nq; p.nr = q->nr; p.nqT = q->nqT;
-    p.n_primal = (q->T + 1) * q->nx + q->T * q->nu;
-    p.n_dual = (q->T + 1) * q->nx + (q->T - 1) * q->nc + q->ncT + 2 * q->T * q->nub + q->T * q->nq + q->nqT + q->T * q->nr;
+// (a) Validates the problem and builds its host side.  No HIP call.
+int build_host_problem(const hmpc_problem &q, const hmpc_options *opt, HostProblem &hp)
+{
+    if (q.nx < 1 || q.nu < 1 || q.nub < 0 || q.nub > q.nu || q.T < 2 || q.nc < 0 || q.ncT < q.nc ||
+        q.nq < 0 || q.nr < 0 || q.nqT < 0)
+        return fail(HMPC_EINVAL, "inconsistent sizes (need nx,nu >= 1, 0 <= nub <= nu, T >= 2, ncT >= nc)");
+    if (!q.A || !q.B || !q.F || !q.G || !q.h || !q.F_Tm1 || !q.G_Tm1 || !q.h_Tm1 || !q.Q || !q.R || !q.Q_T)
+        return fail(HMPC_EINVAL, "null matrix pointer");
+    DevProb &p = hp.p;
+    StageHost &reg = hp.reg;
+    const int nx = q.nx, nu = q.nu, nz = q.nx + q.nu;
+    p.nx = q.nx; p.nu = q.nu; p.nub = q.nub; p.nuc = q.nu - q.nub; p.nz = q.nx + q.nu; p.T = q.T;
+    p.nc = q.nc; p.ncL = q.ncT; p.nT = q.ncT - q.nc; p.mreg = q.nc + 2 * q.nub;
+    p.Toff = q.T * p.mreg; p.M = p.Toff + p.nT; p.Mpad = (p.M + 255) / 256 * 256;
+    p.n = q.T * p.nz + q.nx; p.ne = p.nz * (p.nz + 1) / 2;
+    p.nq = q.nq; p.nr = q.nr; p.nqT = q.nqT;
+    p.n_primal = (q.T + 1) * q.nx + q.T * q.nu;
+    p.n_dual = (q.T + 1) * q.nx + (q.T - 1) * q.nc + q.ncT + 2 * q.T * q.nub + q.T * q.nq + q.nqT + q.T * q.nr;
     p.tol = opt && opt->tol > 0 ? opt->tol : 1e-8;
     p.tol_inf = opt && opt->tol_inf > 0 ? opt->tol_inf : 1e-6;
     p.max_iter = opt && opt->max_iter > 0 ? opt->max_iter : 100;
@@ -372,24 +459,25 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
     p.polish = opt ? opt->polish : 1;
     p.ptol = opt && opt->polish_tol > 0 ? opt->polish_tol : 1e-4;
 
-    StageHost reg;
-    build_stage(*q, q->F, q->G, q->h, q->nc, reg);
+    build_stage(q, q.F, q.G, q.h, q.nc, reg);
+    p.reg.m = reg.m;
+    p.reg.mg = reg.mg;
     p.mreg_magic = (unsigned)((0x100000000ULL + p.mreg - 1) / p.mreg);
     p.nnz0 = (int)reg.rcol.size();
     // columns of the stage rows padded to a fixed stride (compile-time shapes: static column products)
-    std::vector<double> ccv((size_t)nz * HMPC_KC_STRIDE, 0.0);
-    std::vector<int> cci((size_t)nz * HMPC_KC_STRIDE, 0);
+    hp.ccv.assign((size_t)nz * HMPC_KC_STRIDE, 0.0);
+    hp.cci.assign((size_t)nz * HMPC_KC_STRIDE, 0);
     p.kcol = 0;
     for (int j = 0; j < nz; j++) {
         const int len = reg.cptr[j + 1] - reg.cptr[j];
         if (len > p.kcol) p.kcol = len;
         for (int k = 0; k < len && k < HMPC_KC_STRIDE; k++) {
-            ccv[(size_t)j * HMPC_KC_STRIDE + k] = reg.cval[reg.cptr[j] + k];
-            cci[(size_t)j * HMPC_KC_STRIDE + k] = reg.crow[reg.cptr[j] + k];
+            hp.ccv[(size_t)j * HMPC_KC_STRIDE + k] = reg.cval[reg.cptr[j] + k];
+            hp.cci[(size_t)j * HMPC_KC_STRIDE + k] = reg.crow[reg.cptr[j] + k];
         }
     }
     p.static_rows = (p.kcol <= HMPC_KC_STRIDE && p.mreg <= 255) ? 1 : 0;
-    for (int r = 0; r < q->nc; r++) {
+    for (int r = 0; r < q.nc; r++) {
         int cnt = 0;
         for (int j = 0; j < nu; j++) cnt += reg.C[(size_t)r * nz + nx + j] != 0.0;
         if (cnt > 2) p.static_rows = 0;
@@ -397,36 +485,40 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
     p.nng0 = (int)reg.grow.size();
     // The first nc rows of [F_Tm1 G_Tm1 | h_Tm1] must be the stage rows [F G | h] (controller.py:85-87):
     // the last stage then shares the stage lists and only the terminal-set rows are kept apart.
-    for (int r = 0; r < q->nc; r++) {
-        bool same = q->h_Tm1[r] == q->h[r];
-        for (int j = 0; j < nx && same; j++) same = q->F_Tm1[r * nx + j] == q->F[r * nx + j];
-        for (int j = 0; j < nu && same; j++) same = q->G_Tm1[r * nu + j] == q->G[r * nu + j];
-        if (!same) { hmpc_destroy(h); return fail(HMPC_EINVAL, "the first nc rows of F_Tm1, G_Tm1, h_Tm1 must equal F, G, h"); }
+    for (int r = 0; r < q.nc; r++) {
+        bool same = q.h_Tm1[r] == q.h[r];
+        for (int j = 0; j < nx && same; j++) same = q.F_Tm1[r * nx + j] == q.F[r * nx + j];
+        for (int j = 0; j < nu && same; j++) same = q.G_Tm1[r * nu + j] == q.G[r * nu + j];
+        if (!same) return fail(HMPC_EINVAL, "the first nc rows of F_Tm1, G_Tm1, h_Tm1 must equal F, G, h");
     }
     // padded to a whole number of 256-row tiles (zero rows): a lane of the last row slot that has no terminal row
     // still addresses memory of these arrays
     const size_t nTpad = ((size_t)p.nT + 255) / 256 * 256 + 256;
-    std::vector<double> Ct(nTpad * nz, 0.0), ht(nTpad, 0.0), sct(nTpad, 1.0);
+    hp.Ct.assign(nTpad * nz, 0.0);
+    hp.ht.assign(nTpad, 0.0);
+    hp.sct.assign(nTpad, 1.0);
     for (int k = 0; k < p.nT; k++) {
-        const int r = q->nc + k;
+        const int r = q.nc + k;
         double n2 = 0;
-        for (int j = 0; j < nx; j++) n2 += q->F_Tm1[r * nx + j] * q->F_Tm1[r * nx + j];
-        for (int j = 0; j < nu; j++) n2 += q->G_Tm1[r * nu + j] * q->G_Tm1[r * nu + j];
+        for (int j = 0; j < nx; j++) n2 += q.F_Tm1[r * nx + j] * q.F_Tm1[r * nx + j];
+        for (int j = 0; j < nu; j++) n2 += q.G_Tm1[r * nu + j] * q.G_Tm1[r * nu + j];
         const double sc = n2 > 0 ? 1.0 / std::sqrt(n2) : 1.0;
-        sct[k] = sc;
-        for (int j = 0; j < nx; j++) Ct[(size_t)k * nz + j] = sc * q->F_Tm1[r * nx + j];
-        for (int j = 0; j < nu; j++) Ct[(size_t)k * nz + nx + j] = sc * q->G_Tm1[r * nu + j];
-        ht[k] = sc * q->h_Tm1[r];
+        hp.sct[k] = sc;
+        for (int j = 0; j < nx; j++) hp.Ct[(size_t)k * nz + j] = sc * q.F_Tm1[r * nx + j];
+        for (int j = 0; j < nu; j++) hp.Ct[(size_t)k * nz + nx + j] = sc * q.G_Tm1[r * nu + j];
+        hp.ht[k] = sc * q.h_Tm1[r];
     }
 
     // cost Hessians, scaled so that their largest entry is one
-    std::vector<double> P((size_t)nz * nz, 0.0), PT((size_t)nx * nx, 0.0);
+    std::vector<double> &P = hp.P, &PT = hp.PT;
+    P.assign((size_t)nz * nz, 0.0);
+    PT.assign((size_t)nx * nx, 0.0);
     double big = 0;
     for (int i = 0; i < nx; i++)
         for (int j = 0; j < nx; j++) {
             double a = 0, b = 0;
-            for (int k = 0; k < q->nq; k++) a += q->Q[k * nx + i] * q->Q[k * nx + j];
-            for (int k = 0; k < q->nqT; k++) b += q->Q_T[k * nx + i] * q->Q_T[k * nx + j];
+            for (int k = 0; k < q.nq; k++) a += q.Q[k * nx + i] * q.Q[k * nx + j];
+            for (int k = 0; k < q.nqT; k++) b += q.Q_T[k * nx + i] * q.Q_T[k * nx + j];
             P[(size_t)i * nz + j] = 2 * a;
             PT[(size_t)i * nx + j] = 2 * b;
             big = std::fmax(big, std::fmax(std::fabs(2 * a), std::fabs(2 * b)));
@@ -434,7 +526,7 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
     for (int i = 0; i < nu; i++)
         for (int j = 0; j < nu; j++) {
             double a = 0;
-            for (int k = 0; k < q->nr; k++) a += q->R[k * nu + i] * q->R[k * nu + j];
+            for (int k = 0; k < q.nr; k++) a += q.R[k * nu + i] * q.R[k * nu + j];
             P[(size_t)(nx + i) * nz + nx + j] = 2 * a;
             big = std::fmax(big, std::fabs(2 * a));
         }
@@ -448,115 +540,49 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
         p.polish_l1 = cmin >= 1e-2 ? 1 : 0;
     }
 
-    std::vector<int> ei, ej;
-    for (int i = 0; i < nz; i++)
-        for (int j = 0; j <= i; j++) { ei.push_back(i); ej.push_back(j); }
     // Number the entries with a nonempty Gram list first (the register factorisation gives one lane
     // to each of them); the lists follow the same numbering.
     {
+        std::vector<int> ei, ej;
+        for (int i = 0; i < nz; i++)
+            for (int j = 0; j <= i; j++) { ei.push_back(i); ej.push_back(j); }
         std::vector<int> order;
         for (int pass = 0; pass < 2; pass++)
             for (int e = 0; e < p.ne; e++)
                 if ((reg.gptr[e + 1] > reg.gptr[e]) == (pass == 0)) order.push_back(e);
         p.ngram = 0;
         for (int e = 0; e < p.ne; e++) p.ngram += reg.gptr[e + 1] > reg.gptr[e];
-        std::vector<int> ei2, ej2, gptr2(1, 0), grow2;
+        std::vector<int> gptr2(1, 0), grow2;
         std::vector<double> gval2;
         for (int e : order) {
-            ei2.push_back(ei[e]); ej2.push_back(ej[e]);
+            hp.ei.push_back(ei[e]); hp.ej.push_back(ej[e]);
             for (int k = reg.gptr[e]; k < reg.gptr[e + 1]; k++) { grow2.push_back(reg.grow[k]); gval2.push_back(reg.gval[k]); }
             gptr2.push_back((int)grow2.size());
         }
-        ei.swap(ei2); ej.swap(ej2); reg.gptr.swap(gptr2); reg.grow.swap(grow2); reg.gval.swap(gval2);
+        reg.gptr.swap(gptr2); reg.grow.swap(grow2); reg.gval.swap(gval2);
         if (p.ngram > 128) p.static_rows = 0; // (the shipped kernels take 64, hmpc_pick_kernel; kernels compiled for a shape two trips of 64)
     }
+    split_rows(hp);
+    if (p.M >= 65536 || p.mreg >= 65536) return fail(HMPC_ETOOBIG, "more than 65535 constraint rows per node");
+    return HMPC_OK;
+}
 
-    auto vec = [](const double *a, size_t n) { return std::vector<double>(a, a + n); };
-    int rc = HMPC_OK;
-    do {
-        if ((rc = upload_stage(h, reg, p.reg))) break;
-        if ((rc = upload(h, reg.C, &p.Creg))) break;
-        {
-            // dense / singleton split of the stage rows (generic kernel)
-            std::vector<int> drow, rinfo(p.mreg, 0), sptr(nz + 1, 0), srow;
-            std::vector<double> sval(p.mreg, 0.0);
-            for (int r = 0; r < p.mreg; r++) {
-                int cnt = 0, col = 0;
-                for (int j = 0; j < nz; j++)
-                    if (reg.C[(size_t)r * nz + j] != 0.0) { cnt++; col = j; }
-                if (cnt >= 2) { rinfo[r] = -((int)drow.size() + 1); drow.push_back(r); }
-                else { rinfo[r] = col; sval[r] = reg.C[(size_t)r * nz + col]; }
-            }
-            p.nd = (int)drow.size();
-            p.ndp = (p.nd + 3) / 4 * 4;
-            std::vector<double> Cdn((size_t)p.ndp * nz, 0.0);
-            for (int k = 0; k < p.nd; k++)
-                for (int j = 0; j < nz; j++) Cdn[(size_t)k * nz + j] = reg.C[(size_t)drow[k] * nz + j];
-            drow.resize(p.ndp, 0);
-            for (int j = 0; j < nz; j++) {
-                for (int r = 0; r < p.mreg; r++)
-                    if (rinfo[r] == j && sval[r] != 0.0) srow.push_back(r);
-                sptr[j + 1] = (int)srow.size();
-            }
-            p.ns = (int)srow.size();
-            std::vector<int> nrow;
-            for (int r = 0; r < p.mreg; r++)
-                if (rinfo[r] >= 0) nrow.push_back(r);
-            p.nd_magic = p.nd > 0 ? (unsigned)((0x100000000ULL + p.nd - 1) / p.nd) : 0u;
-            p.nn_magic = !nrow.empty() ? (unsigned)((0x100000000ULL + nrow.size() - 1) / nrow.size()) : 0u;
-            if (nrow.empty()) nrow.push_back(0);
-            if ((rc = upload(h, nrow, &p.nrow))) break;
-            if (Cdn.empty()) Cdn.push_back(0.0);
-            if (drow.empty()) drow.push_back(0);
-            if (srow.empty()) srow.push_back(0);
-            if ((rc = upload(h, Cdn, &p.Cdn))) break;
-            if ((rc = upload(h, drow, &p.drow))) break;
-            if ((rc = upload(h, rinfo, &p.rinfo))) break;
-            if ((rc = upload(h, sval, &p.sval))) break;
-            if ((rc = upload(h, sptr, &p.sptr))) break;
-            if ((rc = upload(h, srow, &p.srow))) break;
-        }
-        if ((rc = upload(h, ccv, &p.ccv))) break;
-        if ((rc = upload(h, cci, &p.cci))) break;
-        if ((rc = upload(h, vec(q->F, (size_t)q->nc * nx), &p.F_raw))) break;
-        if ((rc = upload(h, vec(q->G, (size_t)q->nc * nu), &p.G_raw))) break;
-        if ((rc = upload(h, vec(q->h, (size_t)q->nc), &p.h_raw))) break;
-        if ((rc = upload(h, vec(q->h_Tm1, (size_t)q->ncT), &p.hT_raw))) break;
-        if ((rc = upload(h, Ct, &p.Ct))) break;
-        if ((rc = upload(h, ht, &p.ht))) break;
-        if ((rc = upload(h, sct, &p.sct))) break;
-        if ((rc = upload(h, vec(q->A, (size_t)nx * nx), &p.A))) break;
-        if ((rc = upload(h, vec(q->B, (size_t)nx * nu), &p.B))) break;
-        if ((rc = upload(h, P, &p.P))) break;
-        if ((rc = upload(h, PT, &p.PT))) break;
-        if ((rc = upload(h, vec(q->Q, (size_t)q->nq * nx), &p.Q))) break;
-        if ((rc = upload(h, vec(q->R, (size_t)q->nr * nu), &p.R))) break;
-        if ((rc = upload(h, vec(q->Q_T, (size_t)q->nqT * nx), &p.QT))) break;
-        if ((rc = upload(h, ei, &p.ei))) break;
-        if ((rc = upload(h, ej, &p.ej))) break;
-    } while (0);
-    if (rc) { hmpc_destroy(h); return rc; }
-
-    // launch geometry: one 64-lane workgroup per node in flight, as many per CU as LDS admits
-    int cus = 0, lds_max = 0;
-    if (!dry) {
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-    }
-    const size_t lds_cu = 160 * 1024;
-    if (p.M >= 65536 || p.mreg >= 65536) { hmpc_destroy(h); return fail(HMPC_ETOOBIG, "more than 65535 constraint rows per node"); }
+// (b) The kernel of each wave count (1 / 2 / 4 per node) with its LDS carve, and the LDS choices of the problem (DevProb:
+// split_lds, ring).  With `built` (hmpc_jit_build_problem) the kernels compiled for this problem are built, not loaded.
+int choose_kernels(DevProb &p, int lds_max, hmpc_cfg (&cfg)[3], std::vector<void *> &libs, int &jit_kernels, std::vector<std::string> *built)
+{
     // generic kernel on the matrix cores (nz >= 16): the dense stage rows go to LDS if they fit beside everything else
     p.split_lds = 0;
     p.ring = 1;
     if (p.nz >= 16) {
-        const bool big = hmpc_lds_bytes(p, 0, 0) > lds_cu || getenv("HMPC_FORCE_BIG");
+        const bool big = hmpc_lds_bytes(p, 0, 0) > LDS_PER_CU || getenv("HMPC_FORCE_BIG");
         p.split_lds = 1;
-        if (hmpc_lds_bytes(p, 0, big ? 1 : 0) > lds_cu) p.split_lds = 0;
+        if (hmpc_lds_bytes(p, 0, big ? 1 : 0) > LDS_PER_CU) p.split_lds = 0;
     }
     // streaming form: as many stages per chunk of staged multipliers as LDS has room for
     for (int r = 2; r >= 1; r--) { // (two stages per chunk hide the slab latency: the barrier of a chunk costs 0.5 % of a solve)
         p.ring = r;
-        if (hmpc_lds_bytes(p, 0, 1) <= lds_cu) break;
+        if (hmpc_lds_bytes(p, 0, 1) <= LDS_PER_CU) break;
     }
     if (const char *e = getenv("HMPC_RING")) {
         const int r = atoi(e);
@@ -564,37 +590,94 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
     }
     // shapes without a built-in instantiation: the register kernel is compiled now (or found in the cache), hmpc_jit.h
     hmpc_kernel_choice jit[3] = {};
-    // one kernel per number of waves per node; each has its own LDS carve and resident-node count
-    const char *env = getenv("HMPC_BLOCKS_PER_CU");
     for (int pass = 0; pass < 2; pass++) {
         // first the kernels compiled with this problem's sizes (hmpc_jit.h); without them (HMPC_JIT_SIZED=0 / HMPC_JIT=0, no
         // compiler at run time, a compilation that fails) the shipped kernels: the built-in register kernels of the two
         // cart-pole shapes, the run-time-sized kernel for every other system
         const bool sized = pass == 0 && hmpc_sized_enabled();
         if (pass == 0 && !sized) continue;
-        for (int c = 0; c < 3; c++) { jit[c] = hmpc_kernel_choice{}; h->cfg[c] = hmpc_cfg{}; }
-        h->jit_kernels = 0; // (kernels of a first pass that did not complete are not in use)
-        if (sized) hmpc_jit_register_shapes(p, jit, lds_cu);
+        for (int c = 0; c < 3; c++) { jit[c] = hmpc_kernel_choice{}; cfg[c] = hmpc_cfg{}; }
+        jit_kernels = 0; // (kernels of a first pass that did not complete are not in use)
+        if (sized) hmpc_jit_register_shapes(p, jit, LDS_PER_CU);
         for (int c = 0; c < 3; c++) {
-            hmpc_cfg &cf = h->cfg[c];
+            hmpc_cfg &cf = cfg[c];
             cf.k = hmpc_pick_kernel(p, 1 << c, jit);
             cf.lds = hmpc_lds_bytes(p, cf.k.kc, cf.k.big);
-            if (cf.lds > lds_cu || (lds_max > 0 && cf.lds > (size_t)lds_max)) {
+            if (cf.lds > LDS_PER_CU || (lds_max > 0 && cf.lds > (size_t)lds_max)) {
                 char msg[256];
-                snprintf(msg, sizeof msg, "problem needs %zu bytes of LDS per node, more than one CU has (%d)", cf.lds, lds_max > 0 ? lds_max : (int)lds_cu);
-                hmpc_destroy(h);
+                snprintf(msg, sizeof msg, "problem needs %zu bytes of LDS per node, more than one CU has (%d)", cf.lds, lds_max > 0 ? lds_max : (int)LDS_PER_CU);
                 return fail(HMPC_ETOOBIG, msg);
             }
         }
-        if (!sized || hmpc_jit_prepare_sized(p, h->cfg, h->jit_libs, h->jit_kernels, built)) break;
+        if (!sized || hmpc_jit_prepare_sized(p, cfg, libs, jit_kernels, built)) break;
     }
-    if (dry) { delete h; return HMPC_OK; }
+    return HMPC_OK;
+}
+
+// Resident nodes of a kernel with `lds` bytes of LDS per node: as many per CU as LDS admits, at most 8 (HMPC_BLOCKS_PER_CU: another number)
+int resident_grid(size_t lds, int cus, const char *per_cu_env)
+{
+    int per_cu = (int)(LDS_PER_CU / lds);
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu_env && atoi(per_cu_env) > 0) per_cu = atoi(per_cu_env);
+    return (cus > 0 ? cus : 256) * per_cu;
+}
+
+// The first-use check's device block (hmpc_check_compiled): objectives, dual objectives, statuses and iterations of
+// HMPC_CHECK_NODES nodes for each of its three runs, the hand-down index, the records of the compiled kernel's cold run and the
+// check's own nodes -- initial states and fixing vectors (hmpc_check_set_kernel).  Its pinned host mirror has the same layout
+// up to the records (`mirror` bytes).
+struct CheckLayout {
+    size_t obj, dobj, status, iters, idx, primal, dual, x0, fix, mirror, total;
+};
+CheckLayout check_layout(const DevProb &p)
+{
+    constexpr size_t N = HMPC_CHECK_NODES;
+    static_assert(N % 2 == 0, "the records follow N int32 indices: N even keeps them 8-byte aligned");
+    CheckLayout L;
+    L.obj = 0;
+    L.dobj = L.obj + 3 * N * sizeof(double);
+    L.status = L.dobj + 3 * N * sizeof(double);
+    L.iters = L.status + 3 * N * sizeof(int32_t);
+    L.idx = L.iters + 3 * N * sizeof(int32_t);
+    L.primal = L.idx + N * sizeof(int32_t);
+    L.mirror = L.primal;
+    L.dual = L.primal + N * p.n_primal * sizeof(double);
+    L.x0 = L.dual + N * p.n_dual * sizeof(double);
+    L.fix = L.x0 + N * p.nx * sizeof(double);
+    L.total = L.fix + N * p.T * p.nub + 64;
+    return L;
+}
+
+// (c) The device side of a handle whose kernels are chosen: the problem's arrays; the LDS of every kernel (a compiled kernel
+// this device does not take gives way to the shipped one); the shipped kernels the first-use check compares against; the
+// blocks of the check and of the second opinion; the workspaces.
+int setup_device(hmpc_handle *h, const HostProblem &hp, const hmpc_problem &q, int cus, int lds_max)
+{
+    DevProb &p = h->dp;
+    const int nx = q.nx, nu = q.nu;
+    auto vec = [](const double *a, size_t n) { return std::vector<double>(a, a + n); };
+    Uploader up{h->blocks};
+    upload_stage(up, hp.reg, p.reg);
+    up(hp.reg.C, p.Creg);
+    up(hp.nrow, p.nrow); up(hp.Cdn, p.Cdn); up(hp.drow, p.drow); up(hp.rinfo, p.rinfo); up(hp.sval, p.sval); up(hp.sptr, p.sptr); up(hp.srow, p.srow);
+    up(hp.ccv, p.ccv); up(hp.cci, p.cci);
+    up(vec(q.F, (size_t)q.nc * nx), p.F_raw); up(vec(q.G, (size_t)q.nc * nu), p.G_raw); up(vec(q.h, (size_t)q.nc), p.h_raw);
+    up(vec(q.h_Tm1, (size_t)q.ncT), p.hT_raw);
+    up(hp.Ct, p.Ct); up(hp.ht, p.ht); up(hp.sct, p.sct);
+    up(vec(q.A, (size_t)nx * nx), p.A); up(vec(q.B, (size_t)nx * nu), p.B); up(hp.P, p.P); up(hp.PT, p.PT);
+    up(vec(q.Q, (size_t)q.nq * nx), p.Q); up(vec(q.R, (size_t)q.nr * nu), p.R); up(vec(q.Q_T, (size_t)q.nqT * nx), p.QT);
+    up(hp.ei, p.ei); up(hp.ej, p.ej);
+    if (up.rc) return up.rc;
+
+    const char *per_cu_env = getenv("HMPC_BLOCKS_PER_CU");
+    auto fits = [&](size_t lds) { return lds <= LDS_PER_CU && (lds_max <= 0 || lds <= (size_t)lds_max); };
+    auto reserve = [](const hmpc_cfg &f) {
+        return hipFuncSetAttribute((const void *)f.k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) == hipSuccess &&
+               hipFuncSetAttribute((const void *)f.k.fn_warm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) == hipSuccess;
+    };
     for (int c = 0; c < 3; c++) {
         hmpc_cfg &cf = h->cfg[c];
-        auto reserve = [](const hmpc_cfg &f) {
-            return hipFuncSetAttribute((const void *)f.k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) == hipSuccess &&
-                   hipFuncSetAttribute((const void *)f.k.fn_warm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) == hipSuccess;
-        };
         if (!reserve(cf)) {
             // a kernel from the cache that this device does not take (a stale or foreign object: another architecture, another
             // runtime): the shipped kernel of the wave count serves instead, as after a failed first-use check
@@ -608,111 +691,107 @@ static int create_impl(const hmpc_problem *q, const hmpc_options *opt, hmpc_hand
                 cf.sized = 0;
                 cf.ilp = 0;
                 h->jit_rejected++;
-                ok = cf.lds <= lds_cu && (lds_max <= 0 || cf.lds <= (size_t)lds_max) && reserve(cf);
+                ok = fits(cf.lds) && reserve(cf);
             }
-            if (!ok) {
-                hmpc_destroy(h);
-                return fail(HMPC_EDEVICE, "cannot reserve dynamic LDS for the kernel");
-            }
+            if (!ok) return fail(HMPC_EDEVICE, "cannot reserve dynamic LDS for the kernel");
         }
-        int per_cu = (int)(lds_cu / cf.lds);
-        if (per_cu > 8) per_cu = 8;
-        if (env && atoi(env) > 0) per_cu = atoi(env);
-        cf.max_grid = (cus > 0 ? cus : 256) * per_cu;
+        cf.max_grid = resident_grid(cf.lds, cus, per_cu_env);
         if (cf.max_grid > h->max_grid) h->max_grid = cf.max_grid;
     }
     h->lds = h->cfg[0].lds;
     // kernels compiled at hmpc_create are checked against the shipped kernel of the same wave count at their first launch
-    bool ref_big = false;
-    {
-        const char *e = getenv("HMPC_JIT_SELFCHECK");
-        const bool on = !(e && atoi(e) == 0);
-        for (int c = 0; c < 3 && on; c++) {
-            hmpc_cfg &cf = h->cfg[c];
-            const hmpc_kernel_choice ref = hmpc_pick_kernel(p, 1 << c, nullptr);
-            if (ref.fn == cf.k.fn) continue;                            // (a shipped kernel serves: nothing was compiled)
-            const size_t lds = hmpc_lds_bytes(p, ref.kc, ref.big);
-            if (lds > lds_cu || (lds_max > 0 && lds > (size_t)lds_max)) continue;
-            if (hipFuncSetAttribute((const void *)ref.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) continue;
-            if (ref.fn_warm && hipFuncSetAttribute((const void *)ref.fn_warm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError(); // (its list mode is the second opinion's launch: without it that net is off for this wave count)
-                continue;
-            }
-            cf.ref = ref;
-            cf.ref_lds = lds;
-            int per_cu = (int)(lds_cu / lds);
-            if (per_cu > 8) per_cu = 8;
-            cf.ref_grid = (cus > 0 ? cus : 256) * per_cu;
-            if (cf.ref_grid > h->max_grid) h->max_grid = cf.ref_grid;   // (the workspaces below must hold its launches too)
-            ref_big = ref_big || ref.big;
+    const char *e = getenv("HMPC_JIT_SELFCHECK");
+    const bool check = !(e && atoi(e) == 0);
+    bool ref_big = false, any_ref = false;
+    for (int c = 0; c < 3 && check; c++) {
+        hmpc_cfg &cf = h->cfg[c];
+        const hmpc_kernel_choice ref = hmpc_pick_kernel(p, 1 << c, nullptr);
+        if (ref.fn == cf.k.fn) continue;                            // (a shipped kernel serves: nothing was compiled)
+        const size_t lds = hmpc_lds_bytes(p, ref.kc, ref.big);
+        if (!fits(lds)) continue;
+        if (hipFuncSetAttribute((const void *)ref.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) continue;
+        if (ref.fn_warm && hipFuncSetAttribute((const void *)ref.fn_warm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError(); // (its list mode is the second opinion's launch: without it that net is off for this wave count)
+            continue;
         }
-        // ((obj, dual_obj) x 3 runs, (status, iters) x 3 runs, the hand-down index, the records of the compiled kernel's cold run)
-        // ... and the check's own nodes: initial states and fixing vectors (hmpc_check_set_kernel)
-        if (hipMalloc(&h->chk, 3 * HMPC_CHECK_NODES * 2 * sizeof(double) + 3 * HMPC_CHECK_NODES * 2 * sizeof(int32_t) + HMPC_CHECK_NODES * sizeof(int32_t) +
-                                   (size_t)HMPC_CHECK_NODES * (p.n_primal + p.n_dual + p.nx) * sizeof(double) + (size_t)HMPC_CHECK_NODES * p.T * p.nub + 64) != hipSuccess) {
-            hmpc_destroy(h);
-            return fail(HMPC_EDEVICE, "cannot allocate the check block");
-        }
-        // (pinned: an asynchronous copy to or from pageable memory -- the stack arrays this check used until round 5 -- has the
-        // runtime register the pages for its duration, and that bookkeeping did not survive eight host threads checking their
-        // handles at once: heap corruption inside the runtime, one crash in ~30 calls of fleet.closed_loop_parallel with 8 fleets,
-        // none in 180 with the check off; profiles/r05_fleet_trace.txt)
-        if (hipHostMalloc(&h->h_chk, 3 * HMPC_CHECK_NODES * 2 * sizeof(double) + 4 * HMPC_CHECK_NODES * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-            h->h_chk = nullptr;
-            hmpc_destroy(h);
-            return fail(HMPC_EDEVICE, "cannot allocate the check block's host mirror");
-        }
-        // second opinion of hmpc_solve_batch_device: its counts travel to two pinned words behind an event
-        bool any_ref = false;
-        for (int c = 0; c < 3; c++) any_ref = any_ref || h->cfg[c].ref.fn != nullptr;
-        if (any_ref && on) {
-            if (hipHostMalloc((void **)&h->h_hard, 2 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
-                hipEventCreateWithFlags(&h->hard_done, hipEventDisableTiming) != hipSuccess) {
-                hmpc_destroy(h);
-                return fail(HMPC_EDEVICE, "cannot allocate the second-opinion block");
-            }
-        }
+        cf.ref = ref;
+        cf.ref_lds = lds;
+        cf.ref_grid = resident_grid(lds, cus, nullptr);
+        if (cf.ref_grid > h->max_grid) h->max_grid = cf.ref_grid;   // (the workspaces below must hold its launches too)
+        ref_big = ref_big || ref.big;
+        any_ref = true;
     }
+    const CheckLayout L = check_layout(p);
+    if (h->chk.alloc(L.total) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the check block");
+    // (pinned: an asynchronous copy to or from pageable memory -- the stack arrays this check used until round 5 -- has the
+    // runtime register the pages for its duration, and that bookkeeping did not survive eight host threads checking their
+    // handles at once: heap corruption inside the runtime, one crash in ~30 calls of fleet.closed_loop_parallel with 8 fleets,
+    // none in 180 with the check off; profiles/r05_fleet_trace.txt)
+    if (h->h_chk.alloc(L.mirror) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the check block's host mirror");
+    // second opinion of hmpc_solve_batch_device: its counts travel to two pinned words behind an event
+    if (any_ref && (h->h_hard.alloc(2) != hipSuccess || hipEventCreateWithFlags(&h->hard_done, hipEventDisableTiming) != hipSuccess))
+        return fail(HMPC_EDEVICE, "cannot allocate the second-opinion block");
     p.fac_ws = nullptr;
     p.fac_stride = 0;
     if (h->cfg[0].k.big || h->cfg[1].k.big || h->cfg[2].k.big || ref_big) {
         p.fac_stride = p.T * (p.nx * p.nu + p.nu * (p.nu - 1) / 2) + (p.T + 1) * (p.nx * (p.nx + 1) / 2);
-        if (hipMalloc((void **)&p.fac_ws, (size_t)h->max_grid * p.fac_stride * sizeof(double)) != hipSuccess) {
-            hmpc_destroy(h);
-            return fail(HMPC_EDEVICE, "cannot allocate the factor workspace");
-        }
-        h->allocs.push_back(p.fac_ws);
+        if (h->fac_ws.alloc((size_t)h->max_grid * p.fac_stride) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the factor workspace");
+        p.fac_ws = h->fac_ws;
     }
-    if (hipMalloc((void **)&p.work_counter, 2 * sizeof(int)) != hipSuccess) {
-        hmpc_destroy(h);
-        return fail(HMPC_EDEVICE, "cannot allocate the work counter");
-    }
-    h->allocs.push_back(p.work_counter);
+    if (h->work_counter.alloc(2) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the work counter");
+    p.work_counter = h->work_counter;
     (void)hipMemset(p.work_counter, 0, 2 * sizeof(int));
     p.check_flag = (unsigned *)(p.work_counter + 1);
-    if (hipMalloc((void **)&h->rows_ws, (size_t)h->max_grid * 4 * p.Mpad * sizeof(double)) != hipSuccess) {
-        hmpc_destroy(h);
-        return fail(HMPC_EDEVICE, "cannot allocate the row workspace");
-    }
+    if (h->rows_ws.alloc((size_t)h->max_grid * 4 * p.Mpad) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the row workspace");
     if (getenv("HMPC_TRACE")) {
-        (void)hipMalloc((void **)&h->trace, (2 * 64 * 8 + 32) * sizeof(double));
+        (void)h->trace.alloc(2 * 64 * 8 + 32);
         (void)hipMemset(h->trace, 0, (2 * 64 * 8 + 32) * sizeof(double));
     }
-    *out = h;
     return HMPC_OK;
 }
 
-extern "C" int hmpc_create(const hmpc_problem *q, const hmpc_options *opt, hmpc_handle **out) {
-    hmpc_install_backtrace(); return create_impl(q, opt, out, nullptr); }
+} // namespace
+
+extern "C" int hmpc_create(const hmpc_problem *q, const hmpc_options *opt, hmpc_handle **out)
+{
+    hmpc_install_backtrace();
+    g_err.clear();
+    if (!q || !out) return fail(HMPC_EINVAL, "null problem or output pointer");
+    HostProblem hp;
+    int rc = build_host_problem(*q, opt, hp);
+    if (rc) return rc;
+    int dev = opt ? opt->device : -1;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return fail(HMPC_EDEVICE, "no HIP device available");
+    if (hipSetDevice(dev) != hipSuccess) return fail(HMPC_EDEVICE, "hipSetDevice failed");
+    std::unique_ptr<hmpc_handle> h(new hmpc_handle());
+    h->device = dev;
+    h->dp = hp.p;
+    // launch geometry: one 64-lane workgroup per node in flight, as many per CU as LDS admits
+    int cus = 0, lds_max = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    if ((rc = choose_kernels(h->dp, lds_max, h->cfg, h->jit_libs, h->jit_kernels, nullptr))) return rc;
+    if ((rc = setup_device(h.get(), hp, *q, cus, lds_max))) return rc;
+    *out = h.release();
+    return HMPC_OK;
+}
 
 // What hmpc_create would compile for this problem -- the register kernels of its shape, or the run-time-sized kernel with
 // its sizes (hmpc_jit.h) --, compiled into the cache WITHOUT a GPU: packaging, or warming the cache of a machine without a
-// compiler from one that has it.  paths (may be NULL): the shared objects, newline separated.
+// compiler from one that has it.  The host side of hmpc_create up to the choice of kernels; nothing is uploaded or loaded.
+// paths (may be NULL): the shared objects, newline separated.
 extern "C" int hmpc_jit_build_problem(const hmpc_problem *q, const hmpc_options *opt, char *paths, int32_t paths_len)
 {
+    g_err.clear();
+    if (!q) return fail(HMPC_EINVAL, "null problem or output pointer");
+    HostProblem hp;
+    int rc = build_host_problem(*q, opt, hp);
+    if (rc) return rc;
+    hmpc_cfg cfg[3];
+    std::vector<void *> libs;
     std::vector<std::string> built;
-    const int rc = create_impl(q, opt, nullptr, &built);
-    if (rc != HMPC_OK) return rc;
+    int jit_kernels = 0;
+    if ((rc = choose_kernels(hp.p, 0, cfg, libs, jit_kernels, &built))) return rc;
     if (paths && paths_len > 0) {
         std::string all;
         for (const std::string &b : built) all += b + "\n";
@@ -724,25 +803,10 @@ extern "C" int hmpc_jit_build_problem(const hmpc_problem *q, const hmpc_options 
 extern "C" int hmpc_destroy(hmpc_handle *h)
 {
     if (!h) return HMPC_OK;
-    if (h->dry) { delete h; return HMPC_OK; }
     (void)hipSetDevice(h->device);
     // (work this handle issued on a caller's stream may still be in flight -- the counts of a second opinion travel to pinned
     // memory behind an event nobody has waited for: everything on the device ends before anything is freed)
     (void)hipDeviceSynchronize();
-    for (void *d : h->allocs) (void)hipFree(d);
-    if (h->rows_ws) (void)hipFree(h->rows_ws);
-    if (h->order) (void)hipFree(h->order);
-    if (h->pend) (void)hipFree(h->pend);
-    if (h->d_shift) (void)hipFree(h->d_shift);
-    if (h->shift_tv) (void)hipFree(h->shift_tv);
-    if (h->chk) (void)hipFree(h->chk);
-    if (h->h_chk) (void)hipHostFree(h->h_chk);
-    if (h->hard) (void)hipFree(h->hard);
-    if (h->h_hard) (void)hipHostFree(h->h_hard);
-    if (h->hard_done) (void)hipEventDestroy(h->hard_done);
-    if (h->trace) (void)hipFree(h->trace);
-    if (h->d_x0) (void)hipFree(h->d_x0);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
     delete h;
     return HMPC_OK;
 }
@@ -797,34 +861,20 @@ extern "C" int hmpc_set_shift_maps(hmpc_handle *h, const hmpc_shift_maps *m)
     // the retain rule of the shift kernel reads one binary per lane of a wavefront
     if (p.nub > 64) return fail(HMPC_EINVAL, "the node shift supports at most 64 binaries per stage");
     // a second call replaces the maps (the previous device copies are released)
-    for (const double *old : {p.shift_Mmu, p.shift_Mrho, p.shift_V})
-        if (old) {
-            for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-                if (*it == (void *)old) { h->allocs.erase(it); break; }
-            (void)hipFree((void *)old);
-        }
-    p.shift_Mmu = p.shift_Mrho = p.shift_V = nullptr;
-    int rc;
+    h->shift_blocks.clear();
+    p.shift_Mmu = p.shift_Mrho = p.shift_V = h->shift_MT2 = nullptr;
+    // M_mu also in pairs of columns: [pair][row] -> (column 2k, column 2k + 1), an odd last column paired with zeros
+    const size_t ncL2 = ((size_t)p.ncL + 1) / 2;
+    std::vector<double> mt(2 * ncL2 * p.nc, 0.0);
+    for (int r = 0; r < p.nc; r++)
+        for (int k = 0; k < p.ncL; k++) mt[((size_t)(k / 2) * p.nc + r) * 2 + (k & 1)] = m->M_mu[(size_t)r * p.ncL + k];
     auto vec = [](const double *a, size_t n) { return std::vector<double>(a, a + n); };
-    if ((rc = upload(h, vec(m->M_mu, (size_t)p.nc * p.ncL), &p.shift_Mmu))) return rc;
-    if ((rc = upload(h, vec(m->M_rho, (size_t)p.nq * p.nqT), &p.shift_Mrho))) return rc;
-    if ((rc = upload(h, vec(m->V, (size_t)p.nub * p.nu), &p.shift_V))) return rc;
-    {   // [pair of columns][row] -> (column 2k, column 2k + 1), an odd last column paired with zeros
-        const size_t ncL2 = ((size_t)p.ncL + 1) / 2;
-        std::vector<double> mt(2 * ncL2 * p.nc, 0.0);
-        for (int r = 0; r < p.nc; r++)
-            for (int k = 0; k < p.ncL; k++) mt[((size_t)(k / 2) * p.nc + r) * 2 + (k & 1)] = m->M_mu[(size_t)r * p.ncL + k];
-        if (h->shift_MT2) {
-            for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-                if (*it == (void *)h->shift_MT2) { h->allocs.erase(it); break; }
-            (void)hipFree(h->shift_MT2);
-            h->shift_MT2 = nullptr;
-        }
-        const double *dev = nullptr;
-        if ((rc = upload(h, mt, &dev))) return rc;
-        h->shift_MT2 = (double *)dev;
-    }
-    return HMPC_OK;
+    Uploader up{h->shift_blocks};
+    up(vec(m->M_mu, (size_t)p.nc * p.ncL), p.shift_Mmu);
+    up(vec(m->M_rho, (size_t)p.nq * p.nqT), p.shift_Mrho);
+    up(vec(m->V, (size_t)p.nub * p.nu), p.shift_V);
+    up(mt, h->shift_MT2);
+    return up.rc;
 }
 
 static int hmpc_launch_shift(hmpc_handle *h, const ShiftArgs &a, void *stream);
@@ -865,14 +915,7 @@ static int hmpc_launch_shift(hmpc_handle *h, const ShiftArgs &a, void *stream)
         const DevProb &q = h->dp;
         if (!off && h->shift_MT2 && waves >= 4 && q.n_dual >= 2 && q.nub >= 1 && q.nc >= 1 && q.ncL >= 1 && q.nq >= 1 && q.nr >= 1 && q.nx >= 1) {
             const size_t lds = (fixed + (size_t)waves * per) * sizeof(double), need_tv = (size_t)a.K * hmpc_shift_tree_doubles(q);
-            if (need_tv > h->shift_tv_cap) {   // (grows with the number of trees: the stream's earlier launches still read the old block)
-                HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-                if (h->shift_tv) (void)hipFree(h->shift_tv);
-                h->shift_tv = nullptr;
-                h->shift_tv_cap = 0;
-                HIPCHK(hipMalloc((void **)&h->shift_tv, need_tv * sizeof(double)));
-                h->shift_tv_cap = need_tv;
-            }
+            HIPCHK(h->shift_tv.grow(need_tv, need_tv, (hipStream_t)stream)); // (with the number of trees: the stream's earlier launches still read the old block)
             int grid = cus > 0 ? cus : 256;
             const int need = (B + waves - 1) / waves;
             if (grid > need) grid = need;
@@ -926,13 +969,7 @@ extern "C" int hmpc_shift_batch(hmpc_handle *h, int32_t B, int32_t K, const int3
                     {nb, nullptr, dual_obj_out, 0}, {(size_t)B, nullptr, flags, 0}};
     size_t total = 0;
     for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
-    if (total > h->shift_staged) {
-        if (h->d_shift) (void)hipFree(h->d_shift);
-        h->d_shift = nullptr;
-        h->shift_staged = 0;
-        HIPCHK(hipMalloc(&h->d_shift, total));
-        h->shift_staged = total;
-    }
+    HIPCHK(h->d_shift.grow(total, total, nullptr));
     char *base = (char *)h->d_shift;
     for (const Part &q : parts)
         if (q.src) HIPCHK(hipMemcpyAsync(base + q.off, q.src, q.bytes, hipMemcpyHostToDevice, 0));
@@ -974,11 +1011,12 @@ static int hmpc_check_compiled(hmpc_handle *h, hmpc_cfg &cf, const double *d_x0,
     constexpr int N = HMPC_CHECK_NODES;
     const DevProb &p = h->dp;
     const int nfix = p.T * p.nub;
-    double *obj = (double *)h->chk, *dobj = obj + 3 * N;
-    int32_t *st = (int32_t *)(dobj + 3 * N), *it = st + 3 * N, *idx = it + 3 * N;
-    double *prim = (double *)(idx + N + (N & 1)), *dual = prim + (size_t)N * p.n_primal; // (N even: the records stay 8-byte aligned)
-    double *x0c = dual + (size_t)N * p.n_dual;
-    int8_t *fixc = (int8_t *)(x0c + (size_t)N * p.nx);
+    const CheckLayout L = check_layout(p);
+    char *d = h->chk;
+    double *obj = (double *)(d + L.obj), *dobj = (double *)(d + L.dobj);
+    int32_t *st = (int32_t *)(d + L.status), *it = (int32_t *)(d + L.iters), *idx = (int32_t *)(d + L.idx);
+    double *prim = (double *)(d + L.primal), *dual = (double *)(d + L.dual), *x0c = (double *)(d + L.x0);
+    int8_t *fixc = (int8_t *)(d + L.fix);
     hipLaunchKernelGGL(hmpc_check_set_kernel, dim3(N), dim3(256), 0, stream, d_x0, x0_stride, d_fix, B, nfix, p.nx, N, x0c, fixc);
     HIPCHK(hipGetLastError());
     const DevWarm w{nullptr, nullptr, nullptr, nullptr, 0};
@@ -994,8 +1032,9 @@ static int hmpc_check_compiled(hmpc_handle *h, hmpc_cfg &cf, const double *d_x0,
         HIPCHK(hipGetLastError());
     }
     if (!h->h_chk) return HMPC_OK;
-    double *hobj = (double *)h->h_chk, *hdob = hobj + 3 * N;   // (pinned, see hmpc_create)
-    int32_t *hst = (int32_t *)(hdob + 3 * N), *hidx = hst + 3 * N;
+    char *hm = h->h_chk;   // (pinned, see setup_device)
+    double *hobj = (double *)(hm + L.obj), *hdob = (double *)(hm + L.dobj);
+    int32_t *hst = (int32_t *)(hm + L.status), *hidx = (int32_t *)(hm + L.idx);
     HIPCHK(hipMemcpyAsync(hobj, obj, 2 * N * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(hdob, dobj, 2 * N * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(hst, st, 2 * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -1135,14 +1174,7 @@ extern "C" int hmpc_solve_batch_device(hmpc_handle *h, const double *d_x0, int32
     // more nodes than resident workgroups: hand them out shallow first (hmpc_order_kernel)
     int32_t *order = nullptr;
     if (B > grid + grid / 8 && !getenv("HMPC_NO_ORDER")) {
-        if (B > h->order_cap) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            if (h->order) (void)hipFree(h->order);
-            h->order = nullptr;
-            h->order_cap = 0;
-            HIPCHK(hipMalloc((void **)&h->order, (size_t)(B + B / 2) * sizeof(int32_t)));
-            h->order_cap = B + B / 2;
-        }
+        HIPCHK(h->order.grow(B, B + B / 2, (hipStream_t)stream));
         order = h->order;
         hipLaunchKernelGGL(hmpc_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_fix, B, h->dp.T * h->dp.nub, order, w,
                            (h->dp.T + 1) * h->dp.nx + (h->dp.T - 1) * h->dp.nc + h->dp.nc, h->dp.nT, h->dp.n_dual);
@@ -1161,14 +1193,7 @@ extern "C" int hmpc_solve_batch_device(hmpc_handle *h, const double *d_x0, int32
     const bool split = !w.index && nw == 1 && k.kc > 0 && c4.k.kc > 0 && h->dp.nT > 0 && h->dp.lazy && h->dp.polish && o.primal && o.dual && o.iters &&
                        o.status && getenv("HMPC_SPLIT") && !h->trace;
     if (split) {
-        if (B + 1 > h->pend_cap) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            if (h->pend) (void)hipFree(h->pend);
-            h->pend = nullptr;
-            h->pend_cap = 0;
-            HIPCHK(hipMalloc((void **)&h->pend, (size_t)(B + B / 2 + 1) * sizeof(int32_t)));
-            h->pend_cap = B + B / 2 + 1;
-        }
+        HIPCHK(h->pend.grow(B + 1, B + B / 2 + 1, (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(h->pend, 0, sizeof(int32_t), (hipStream_t)stream));
         w.pend = h->pend;
     }
@@ -1193,14 +1218,7 @@ extern "C" int hmpc_solve_batch_device(hmpc_handle *h, const double *d_x0, int32
     // The counts travel to the host behind an event and are looked at by the next call (hmpc_second_opinion_review_impl).
     // Every entry that solves goes through here: hmpc_solve_batch, hmpc_fleet_solve, callers with device pointers.
     if (cfm.ref.fn && k.fn != cfm.ref.fn && cfm.ref.fn_warm && o.status && !h->trace && !split && cfm.second_opinions < 3 && h->hard_done) {
-        if (B + 4 > h->hard_cap) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            if (h->hard) (void)hipFree(h->hard);
-            h->hard = nullptr;
-            h->hard_cap = 0;
-            HIPCHK(hipMalloc((void **)&h->hard, (size_t)(B + B / 2 + 4) * sizeof(int32_t)));
-            h->hard_cap = B + B / 2 + 4;
-        }
+        HIPCHK(h->hard.grow(B + 4, B + B / 2 + 4, (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(h->hard, 0, 3 * sizeof(int32_t), (hipStream_t)stream));
         hipLaunchKernelGGL(hmpc_hard_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int32_t *)o.status, B, h->hard + 2);
         HIPCHK(hipGetLastError());
@@ -1249,20 +1267,14 @@ static StageLayout stage_layout(const DevProb &p, size_t B, size_t nw = 0)
     return L;
 }
 
-static int ensure_staging(hmpc_handle *h, int B, bool with_warm)
+// Room in both staging blocks for a batch of B nodes, nw of them with a parent record; a block that is short is replaced by one
+// for 64 nodes, or B + B / 4 from 64 on (each with room for a record if any of this batch has one)
+static int ensure_staging(hmpc_handle *h, size_t B, size_t nw)
 {
-    if (B <= h->staged && (!with_warm || h->staged_warm)) return HMPC_OK;
-    if (h->d_x0) { (void)hipFree(h->d_x0); h->d_x0 = nullptr; }
-    if (h->h_stage) { (void)hipHostFree(h->h_stage); h->h_stage = nullptr; }
-    const int want = B > h->staged ? B : h->staged;
-    h->staged = 0;
-    const int cap = want < 64 ? 64 : want + want / 4;
-    with_warm = with_warm || h->staged_warm;
-    const StageLayout L = stage_layout(h->dp, (size_t)cap, with_warm ? (size_t)cap : 0);
-    HIPCHK(hipMalloc(&h->d_x0, L.total));
-    HIPCHK(hipHostMalloc(&h->h_stage, L.total, hipHostMallocDefault));
-    h->staged = cap;
-    h->staged_warm = with_warm;
+    const size_t cap = B < 64 ? 64 : B + B / 4;
+    const size_t want = stage_layout(h->dp, B, nw).total, room = stage_layout(h->dp, cap, nw ? cap : 0).total;
+    HIPCHK(h->d_stage.grow(want, room, nullptr));
+    HIPCHK(h->h_stage.grow(want, room, nullptr));
     return HMPC_OK;
 }
 
@@ -1284,12 +1296,12 @@ extern "C" int hmpc_solve_batch(hmpc_handle *h, const double *x0, int32_t x0_str
             nwarm += warm->index[b] >= 0;
         }
     }
-    int rc = ensure_staging(h, B, nwarm > 0);
+    int rc = ensure_staging(h, (size_t)B, nwarm);
     if (rc) return rc;
     // offsets of THIS batch (they always fit the capacity the blocks were allocated for): with the capacity's offsets
     // a small branch-and-bound round after one large call dragged the whole capacity-sized primal region along
     const StageLayout L = stage_layout(p, (size_t)B, nwarm);
-    char *hs = (char *)h->h_stage, *ds = (char *)h->d_x0;
+    char *hs = h->h_stage, *ds = h->d_stage;
     const size_t nfix = (size_t)p.T * p.nub;
     if (x0_stride == 0) std::memcpy(hs + L.x0, x0, p.nx * sizeof(double));
     else

@@ -13,15 +13,24 @@ struct hmpc_comm {
     hmpc_handle *h = nullptr;
     void *lib = nullptr;
     void *comm = nullptr; // ncclComm_t
-    double *d_pair = nullptr, *h_pair = nullptr;
-    int8_t *d_bytes = nullptr;
-    size_t cap_bytes = 0;
+    DevBuf<double> d_pair;
+    PinBuf<double> h_pair;
+    DevBuf<int8_t> d_bytes; // T * nub bytes
     int rank = 0, nranks = 1;
     hipStream_t stream = nullptr;
     int (*AllReduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
     int (*Broadcast)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
     int (*CommDestroy)(void *) = nullptr;
     const char *(*GetErrorString)(int) = nullptr;
+    hmpc_comm() = default;
+    hmpc_comm(const hmpc_comm &) = delete;
+    hmpc_comm &operator=(const hmpc_comm &) = delete;
+    // the stream ends and goes first, then the communicator; the buffers are released after this body
+    ~hmpc_comm()
+    {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (comm && CommDestroy) (void)CommDestroy(comm);
+    }
 };
 
 namespace {
@@ -52,36 +61,29 @@ extern "C" int hmpc_comm_create(hmpc_handle *h, int32_t nranks, int32_t rank, co
     g_err.clear();
     if (!h || !id128 || !out || nranks < 1 || rank < 0 || rank >= nranks) return fail(HMPC_EINVAL, "comm: bad argument");
     HIPCHK(hipSetDevice(h->device));
-    hmpc_comm *c = new hmpc_comm();
+    std::unique_ptr<hmpc_comm> c(new hmpc_comm());
     c->h = h;
     c->rank = rank;
     c->nranks = nranks;
     c->lib = rccl_open();
-    if (!c->lib) { delete c; return fail(HMPC_EDEVICE, "comm: cannot load RCCL"); }
+    if (!c->lib) return fail(HMPC_EDEVICE, "comm: cannot load RCCL");
     auto init = (int (*)(void **, int, RcclId, int))dlsym(c->lib, "ncclCommInitRank");
     c->AllReduce = (int (*)(const void *, void *, size_t, int, int, void *, hipStream_t))dlsym(c->lib, "ncclAllReduce");
     c->Broadcast = (int (*)(const void *, void *, size_t, int, int, void *, hipStream_t))dlsym(c->lib, "ncclBroadcast");
     c->CommDestroy = (int (*)(void *))dlsym(c->lib, "ncclCommDestroy");
     c->GetErrorString = (const char *(*)(int))dlsym(c->lib, "ncclGetErrorString");
-    if (!init || !c->AllReduce || !c->Broadcast || !c->CommDestroy) { delete c; return fail(HMPC_EDEVICE, "comm: RCCL symbols not found"); }
+    if (!init || !c->AllReduce || !c->Broadcast || !c->CommDestroy) return fail(HMPC_EDEVICE, "comm: RCCL symbols not found");
     RcclId id;
     std::memcpy(id.bytes, id128, sizeof id.bytes);
     const int rc = init(&c->comm, nranks, id, rank);
-    if (rc != 0) {
-        std::string msg = std::string("comm: ncclCommInitRank failed: ") + (c->GetErrorString ? c->GetErrorString(rc) : "?");
-        delete c;
-        return fail(HMPC_EDEVICE, msg);
-    }
+    if (rc != 0) return fail(HMPC_EDEVICE, std::string("comm: ncclCommInitRank failed: ") + (c->GetErrorString ? c->GetErrorString(rc) : "?"));
     // (everything a later collective needs is allocated here: an allocation that fails between two collectives would
     // leave the other ranks waiting in the next one)
-    c->cap_bytes = (size_t)std::max(1, h->dp.T * h->dp.nub);
-    if (hipMalloc((void **)&c->d_pair, 2 * sizeof(double)) != hipSuccess || hipHostMalloc((void **)&c->h_pair, 2 * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&c->d_bytes, c->cap_bytes) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        hmpc_comm_destroy(c);
+    if (c->d_pair.alloc(2) != hipSuccess || c->h_pair.alloc(2) != hipSuccess ||
+        c->d_bytes.alloc((size_t)std::max(1, h->dp.T * h->dp.nub)) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return fail(HMPC_EDEVICE, "comm: cannot allocate");
-    }
-    *out = c;
+    *out = c.release();
     return HMPC_OK;
 }
 
@@ -140,7 +142,7 @@ extern "C" int hmpc_publish_incumbent(hmpc_comm *c, double *ub, int8_t *assignme
     // (a failure between two collectives aborts the communicator: the peers are already in the next one.  Nothing below
     // can fail for a reason of this rank alone -- the staging buffer is allocated at creation --, and a bound that is no
     // bound is seen by EVERY rank after the first reduction: all of them return the error together)
-    if ((size_t)nbytes > c->cap_bytes) return fail(HMPC_EINVAL, "comm: assignment longer than T * nub of the handle the communicator was created on");
+    if ((size_t)nbytes > c->d_bytes.size()) return fail(HMPC_EINVAL, "comm: assignment longer than T * nub of the handle the communicator was created on");
     const double mine = (*ub == *ub) ? *ub : -std::numeric_limits<double>::infinity(); // (NaN: no order under MIN)
     double best = 0, who = 0;
     int rc;
@@ -165,11 +167,6 @@ extern "C" int hmpc_comm_destroy(hmpc_comm *c)
 {
     if (!c) return HMPC_OK;
     (void)hipSetDevice(c->h->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->comm && c->CommDestroy) (void)c->CommDestroy(c->comm);
-    if (c->d_pair) (void)hipFree(c->d_pair);
-    if (c->d_bytes) (void)hipFree(c->d_bytes);
-    if (c->h_pair) (void)hipHostFree(c->h_pair);
     delete c;
     return HMPC_OK;
 }

@@ -31,25 +31,28 @@ struct hmpc_fleet {
     hmpc_handle *h = nullptr;
     int K = 0;
     std::vector<FleetTree> trees;
-    hipStream_t stream = nullptr;
-    double *pool[2] = {nullptr, nullptr}, *dobj[2] = {nullptr, nullptr};
-    double *ppool = nullptr; // primal rows of the current step's solved nodes (same row index as pool[cur])
-    size_t cap_rows = 0, used = 0;
+    hipStream_t stream = nullptr; // (destroyed after the buffers below are released: hmpc_fleet_destroy)
+    DevBuf<double> pool[2], dobj[2]; // rows: dobj[s].size()
+    DevBuf<double> ppool; // primal rows of the current step's solved nodes (same row index as pool[cur])
+    size_t used = 0;
     int cur = 0;
-    // per-round device buffers and their pinned host mirrors
-    size_t cap_b = 0;
-    int8_t *d_fix = nullptr, *h_fix = nullptr, *d_fix_out = nullptr;
-    double *d_x0 = nullptr, *h_x0 = nullptr, *d_obj = nullptr, *h_obj = nullptr, *d_primal = nullptr, *h_nu = nullptr;
-    int32_t *d_status = nullptr, *h_status = nullptr, *d_iters = nullptr, *h_iters = nullptr;
-    int32_t *d_owner = nullptr, *h_owner = nullptr, *d_src = nullptr, *h_src = nullptr, *d_widx = nullptr, *h_widx = nullptr;
+    // per-round device buffers and their pinned host mirrors (fleet_ensure_round)
+    DevBuf<int8_t> d_fix, d_fix_out;
+    PinBuf<int8_t> h_fix;
+    DevBuf<double> d_x0, d_obj, d_lb, d_lb_out;
+    PinBuf<double> h_x0, h_obj, h_nu, h_lb;
+    DevBuf<int32_t> d_status, d_iters, d_owner, d_src, d_widx;
+    PinBuf<int32_t> h_status, h_iters, h_owner, h_src, h_widx;
+    DevBuf<uint8_t> d_flags;
+    PinBuf<uint8_t> h_flags;
     int handdown = 1; // parent -> child hand-down of active sets (hmpc_fleet_options)
-    double *d_lb = nullptr, *h_lb = nullptr, *d_lb_out = nullptr;
-    uint8_t *d_flags = nullptr, *h_flags = nullptr;
-    double *d_kx0 = nullptr, *d_ku0 = nullptr, *d_ke0 = nullptr, *h_k = nullptr; // K x nx, K x nu, K x nx (pinned: 3 blocks)
-    double *h_bits = nullptr;                                                  // dive prediction: primal rows of a round's nodes (pinned)
-    size_t cap_bits = 0;
-    double *h_prow = nullptr, *d_prow = nullptr;                               // K primal rows: pinned / device (incumbents of a step)
-    int32_t *h_inc = nullptr, *d_inc = nullptr;                                // K: pool row of each loop's incumbent
+    DevBuf<double> d_kx0, d_ku0, d_ke0; // K x nx, K x nu, K x nx
+    PinBuf<double> h_k;                 //   their pinned mirror (3 blocks)
+    PinBuf<double> h_bits;              // dive prediction: primal rows of a round's nodes
+    PinBuf<double> h_prow;              // K primal rows: pinned / device (incumbents of a step)
+    DevBuf<double> d_prow;
+    PinBuf<int32_t> h_inc;              // K: pool row of each loop's incumbent
+    DevBuf<int32_t> d_inc;
     long long rounds = 0, launched = 0, handed = 0;
     long long uncertified = 0, resting = 0; // nodes pruned without a certificate; searches whose optimum rests on such a prune (hmpc_fleet_uncertified)
     double t_select = 0, t_stage = 0, t_device = 0, t_consume = 0, t_shift = 0; // host wall time by phase (hmpc_fleet_timing)
@@ -75,86 +78,39 @@ int fleet_fail(hmpc_fleet *f, int code, const std::string &msg)
     return fail(code, msg + " -- the fleet must be reset (hmpc_fleet_reset(f, -1)) before it is used again");
 }
 
-template <class T> int dev_alloc(T **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(T)) == hipSuccess ? 0 : -1; }
-template <class T> int pin_alloc(T **p, size_t n) { return hipHostMalloc((void **)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault) == hipSuccess ? 0 : -1; }
-
-void fleet_free_round(hmpc_fleet *f)
-{
-    for (void *d : {(void *)f->d_fix, (void *)f->d_fix_out, (void *)f->d_x0, (void *)f->d_obj, (void *)f->d_primal, (void *)f->d_status, (void *)f->d_iters,
-                    (void *)f->d_owner, (void *)f->d_src, (void *)f->d_widx, (void *)f->d_lb, (void *)f->d_lb_out, (void *)f->d_flags})
-        if (d) (void)hipFree(d);
-    for (void *d : {(void *)f->h_fix, (void *)f->h_x0, (void *)f->h_obj, (void *)f->h_nu, (void *)f->h_status, (void *)f->h_iters, (void *)f->h_owner,
-                    (void *)f->h_src, (void *)f->h_widx, (void *)f->h_lb, (void *)f->h_flags})
-        if (d) (void)hipHostFree(d);
-    f->d_fix = f->h_fix = f->d_fix_out = nullptr;
-    f->d_x0 = f->h_x0 = f->d_obj = f->h_obj = f->d_primal = f->h_nu = nullptr;
-    f->d_status = f->h_status = f->d_iters = f->h_iters = nullptr;
-    f->d_owner = f->h_owner = f->d_src = f->h_src = f->d_widx = f->h_widx = nullptr;
-    f->d_lb = f->h_lb = f->d_lb_out = nullptr;
-    f->d_flags = f->h_flags = nullptr;
-    f->cap_b = 0;
-}
-
+// Room in the round buffers for B nodes: one that is short is replaced by room for max(2B, 1024) nodes.
 int fleet_ensure_round(hmpc_fleet *f, size_t B)
 {
-    if (B <= f->cap_b) return HMPC_OK;
-    HIPCHK(hipStreamSynchronize(f->stream));
-    fleet_free_round(f);
     const DevProb &p = f->h->dp;
     const size_t cap = std::max<size_t>(2 * B, 1024), nfix = (size_t)p.T * p.nub;
-    int bad = 0;
-    bad |= dev_alloc(&f->d_fix, cap * nfix) | pin_alloc(&f->h_fix, cap * nfix) | dev_alloc(&f->d_fix_out, cap * nfix);
-    bad |= dev_alloc(&f->d_x0, cap * p.nx) | pin_alloc(&f->h_x0, cap * p.nx);
-    bad |= dev_alloc(&f->d_obj, cap) | pin_alloc(&f->h_obj, cap);
-    bad |= pin_alloc(&f->h_nu, cap * 2 * nfix);
-    bad |= dev_alloc(&f->d_status, cap) | pin_alloc(&f->h_status, cap) | dev_alloc(&f->d_iters, cap) | pin_alloc(&f->h_iters, cap);
-    bad |= dev_alloc(&f->d_owner, cap) | pin_alloc(&f->h_owner, cap) | dev_alloc(&f->d_src, cap) | pin_alloc(&f->h_src, cap);
-    bad |= dev_alloc(&f->d_widx, cap) | pin_alloc(&f->h_widx, cap);
-    bad |= dev_alloc(&f->d_lb, cap) | pin_alloc(&f->h_lb, cap) | dev_alloc(&f->d_lb_out, cap);
-    bad |= dev_alloc(&f->d_flags, cap) | pin_alloc(&f->h_flags, cap);
-    if (bad) return fail(HMPC_EDEVICE, "fleet: cannot allocate the round buffers");
-    f->cap_b = cap;
+    hipError_t e = hipSuccess;
+    auto grow = [&](auto &buf, size_t per_node) { if (e == hipSuccess) e = buf.grow(B * per_node, cap * per_node, f->stream); };
+    grow(f->d_fix, nfix); grow(f->h_fix, nfix); grow(f->d_fix_out, nfix);
+    grow(f->d_x0, p.nx); grow(f->h_x0, p.nx);
+    grow(f->d_obj, 1); grow(f->h_obj, 1);
+    grow(f->h_nu, 2 * nfix);
+    grow(f->d_status, 1); grow(f->h_status, 1); grow(f->d_iters, 1); grow(f->h_iters, 1);
+    grow(f->d_owner, 1); grow(f->h_owner, 1); grow(f->d_src, 1); grow(f->h_src, 1);
+    grow(f->d_widx, 1); grow(f->h_widx, 1);
+    grow(f->d_lb, 1); grow(f->h_lb, 1); grow(f->d_lb_out, 1);
+    grow(f->d_flags, 1); grow(f->h_flags, 1);
+    if (e != hipSuccess) return fail(HMPC_EDEVICE, "fleet: cannot allocate the round buffers");
     return HMPC_OK;
 }
 
-// Room for `rows` rows in both pools; the rows in use of the current pool are kept.
+// Room for `rows` rows in both pools (max(rows + rows / 2, 4096) where short); the rows in use of the current pool are kept.
 int fleet_ensure_rows(hmpc_fleet *f, size_t rows)
 {
-    if (rows <= f->cap_rows) return HMPC_OK;
-    HIPCHK(hipStreamSynchronize(f->stream));
     const DevProb &p = f->h->dp;
     const size_t cap = std::max<size_t>(rows + rows / 2, 4096);
-    for (int s = 0; s < 2; s++) {
-        double *np_ = nullptr, *nd = nullptr;
-        if (dev_alloc(&np_, cap * p.n_dual) || dev_alloc(&nd, cap)) {
-            if (np_) (void)hipFree(np_);
-            if (nd) (void)hipFree(nd);
-            return fail(HMPC_EDEVICE, "fleet: cannot grow the row pools");
-        }
-        if (s == f->cur && f->used) {
-            if (hipMemcpy(np_, f->pool[s], f->used * p.n_dual * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess ||
-                hipMemcpy(nd, f->dobj[s], f->used * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) {
-                (void)hipFree(np_);
-                (void)hipFree(nd);
-                return fail(HMPC_EDEVICE, "fleet: cannot copy the row pools");
-            }
-        }
-        if (f->pool[s]) (void)hipFree(f->pool[s]);
-        if (f->dobj[s]) (void)hipFree(f->dobj[s]);
-        f->pool[s] = np_;
-        f->dobj[s] = nd;
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < 2 && e == hipSuccess; s++) {
+        const size_t keep = s == f->cur ? f->used : 0;
+        e = f->pool[s].grow(rows * p.n_dual, cap * p.n_dual, f->stream, keep * p.n_dual);
+        if (e == hipSuccess) e = f->dobj[s].grow(rows, cap, f->stream, keep);
     }
-    {
-        double *pp = nullptr;
-        if (dev_alloc(&pp, cap * p.n_primal)) return fail(HMPC_EDEVICE, "fleet: cannot grow the row pools");
-        if (f->ppool && f->used && hipMemcpy(pp, f->ppool, f->used * p.n_primal * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess) {
-            (void)hipFree(pp);
-            return fail(HMPC_EDEVICE, "fleet: cannot copy the row pools");
-        }
-        if (f->ppool) (void)hipFree(f->ppool);
-        f->ppool = pp;
-    }
-    f->cap_rows = cap;
+    if (e == hipSuccess) e = f->ppool.grow(rows * p.n_primal, cap * p.n_primal, f->stream, f->used * p.n_primal);
+    if (e != hipSuccess) return fail(HMPC_EDEVICE, "fleet: cannot grow the row pools");
     return HMPC_OK;
 }
 
@@ -166,7 +122,7 @@ extern "C" int hmpc_fleet_create(hmpc_handle *h, int32_t K, hmpc_fleet **out)
     if (!h || !out || K < 1) return fail(HMPC_EINVAL, "fleet: null handle or K < 1");
     if (!h->dp.shift_Mmu) return fail(HMPC_EINVAL, "fleet: hmpc_set_shift_maps has not been called");
     HIPCHK(hipSetDevice(h->device));
-    hmpc_fleet *f = new hmpc_fleet();
+    std::unique_ptr<hmpc_fleet> f(new hmpc_fleet());
     f->h = h;
     f->K = K;
     const DevProb &p = h->dp;
@@ -175,12 +131,14 @@ extern "C" int hmpc_fleet_create(hmpc_handle *h, int32_t K, hmpc_fleet **out)
         tree_reset_cold(t, p.T * p.nub);
         t.x0.assign(p.nx, 0.0);
     }
-    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) { delete f; return fail(HMPC_EDEVICE, "fleet: cannot create a stream"); }
-    int bad = dev_alloc(&f->d_kx0, (size_t)K * p.nx) | dev_alloc(&f->d_ku0, (size_t)K * p.nu) | dev_alloc(&f->d_ke0, (size_t)K * p.nx);
-    bad |= pin_alloc(&f->h_k, (size_t)K * (2 * p.nx + p.nu)) | pin_alloc(&f->h_prow, (size_t)K * p.n_primal) | dev_alloc(&f->d_prow, (size_t)K * p.n_primal);
-    bad |= pin_alloc(&f->h_inc, (size_t)K) | dev_alloc(&f->d_inc, (size_t)K);
-    if (bad) { hmpc_fleet_destroy(f); return fail(HMPC_EDEVICE, "fleet: cannot allocate"); }
-    *out = f;
+    const bool ok = f->d_kx0.alloc((size_t)K * p.nx) == hipSuccess && f->d_ku0.alloc((size_t)K * p.nu) == hipSuccess &&
+                    f->d_ke0.alloc((size_t)K * p.nx) == hipSuccess && f->h_k.alloc((size_t)K * (2 * p.nx + p.nu)) == hipSuccess &&
+                    f->h_prow.alloc((size_t)K * p.n_primal) == hipSuccess && f->d_prow.alloc((size_t)K * p.n_primal) == hipSuccess &&
+                    f->h_inc.alloc((size_t)K) == hipSuccess && f->d_inc.alloc((size_t)K) == hipSuccess;
+    if (!ok) return fail(HMPC_EDEVICE, "fleet: cannot allocate");
+    // (the stream last: nothing else of the fleet is left to release if it cannot be created)
+    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) return fail(HMPC_EDEVICE, "fleet: cannot create a stream");
+    *out = f.release();
     return HMPC_OK;
 }
 
@@ -188,20 +146,10 @@ extern "C" int hmpc_fleet_destroy(hmpc_fleet *f)
 {
     if (!f) return HMPC_OK;
     (void)hipSetDevice(f->h->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    fleet_free_round(f);
-    for (int s = 0; s < 2; s++) {
-        if (f->pool[s]) (void)hipFree(f->pool[s]);
-        if (f->dobj[s]) (void)hipFree(f->dobj[s]);
-    }
-    for (void *d : {(void *)f->d_kx0, (void *)f->d_ku0, (void *)f->d_ke0, (void *)f->ppool, (void *)f->d_prow, (void *)f->d_inc})
-        if (d) (void)hipFree(d);
-    if (f->h_k) (void)hipHostFree(f->h_k);
-    if (f->h_prow) (void)hipHostFree(f->h_prow);
-    if (f->h_inc) (void)hipHostFree(f->h_inc);
-    if (f->h_bits) (void)hipHostFree(f->h_bits);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
+    const hipStream_t stream = f->stream;
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete f; // (releases every buffer)
+    if (stream) (void)hipStreamDestroy(stream);
     return HMPC_OK;
 }
 
@@ -230,7 +178,7 @@ extern "C" int hmpc_fleet_rows(const hmpc_fleet *f, int64_t *used, int64_t *capa
 {
     if (!f) return fail(HMPC_EINVAL, "fleet: null argument");
     if (used) *used = (int64_t)f->used;
-    if (capacity) *capacity = (int64_t)f->cap_rows;
+    if (capacity) *capacity = (int64_t)f->dobj[0].size();
     return HMPC_OK;
 }
 
@@ -336,14 +284,8 @@ extern "C" int hmpc_fleet_solve(hmpc_fleet *f, const double *x0, int32_t width, 
             HIPCHK(hipMemcpyAsync(f->h_status, f->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
             HIPCHK(hipMemcpyAsync(f->h_iters, f->d_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
             if (dive) { // the round's primal rows: the rounded binaries of its vertex nodes predict their descendants' dives
-                if (B > f->cap_bits) {
-                    HIPCHK(hipStreamSynchronize(f->stream));
-                    if (f->h_bits) (void)hipHostFree(f->h_bits);
-                    f->h_bits = nullptr;
-                    f->cap_bits = 0;
-                    if (pin_alloc(&f->h_bits, 2 * B * p.n_primal)) return fail(HMPC_EDEVICE, "fleet: cannot allocate the prediction buffer");
-                    f->cap_bits = 2 * B;
-                }
+                if (f->h_bits.grow(B * p.n_primal, 2 * B * p.n_primal, f->stream) != hipSuccess)
+                    return fail(HMPC_EDEVICE, "fleet: cannot allocate the prediction buffer");
                 HIPCHK(hipMemcpyAsync(f->h_bits, f->ppool + f->used * p.n_primal, B * p.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
             }
             HIPCHK(hipMemcpy2DAsync(f->h_nu, 2 * nfix * sizeof(double), rows + o_lb, p.n_dual * sizeof(double), 2 * nfix * sizeof(double), B,

@@ -373,20 +373,6 @@ static size_t hmpc_lp_lds_bytes(int n, int m, int a_in_lds)
 }
 
 // ---- C ABI (declared in include/hmpc.h) ----
-namespace {
-struct LpBuffers {   // freed on every exit path
-    std::vector<void *> ptrs;
-    ~LpBuffers() { for (void *q : ptrs) if (q) (void)hipFree(q); }
-    template <class T> hipError_t get(T **out, size_t count)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(q);
-        *out = (T *)q;
-        return e;
-    }
-};
-} // namespace
 
 extern "C" int hmpc_lp_solve_batch(int32_t device, int32_t n, int32_t m, const double *A, const double *c, int32_t c_stride,
                                    const double *b, int32_t b_stride, const int32_t *relax, int32_t B, double tol,
@@ -416,22 +402,22 @@ extern "C" int hmpc_lp_solve_batch(int32_t device, int32_t n, int32_t m, const d
         rs[r] = a > 0 ? 1.0 / std::sqrt(a) : 1.0;
         for (int j = 0; j < n; j++) At[(size_t)j * m + r] = A[(size_t)r * n + j] * rs[r];
     }
-    LpBuffers buf;
     LpArgs a{};
     a.n = n; a.m = m; a.B = B; a.c_stride = c_stride; a.b_stride = b_stride; a.max_iter = max_iter; a.tol = tol;
     a.a_in_lds = hmpc_lp_lds_bytes(n, m, 1) <= (size_t)lds_max;
-    double *dAt, *drs, *dc, *db;
-    int32_t *drelax = nullptr;
+    DevBuf<double> dAt, drs, dc, db, dobj, dx, dz;
+    DevBuf<int32_t> drelax, dstatus, diters;
     const size_t nc = c_stride ? (size_t)B * n : n, nb = b_stride ? (size_t)B * m : m;
-    HIPCHK(buf.get(&dAt, At.size())); HIPCHK(buf.get(&drs, m)); HIPCHK(buf.get(&dc, nc)); HIPCHK(buf.get(&db, nb));
-    HIPCHK(buf.get(&a.obj, B)); HIPCHK(buf.get(&a.x, (size_t)B * n)); HIPCHK(buf.get(&a.status, B)); HIPCHK(buf.get(&a.iters, B));
-    if (z) HIPCHK(buf.get(&a.z, (size_t)B * m));
-    if (relax) { HIPCHK(buf.get(&drelax, B)); HIPCHK(hipMemcpy(drelax, relax, sizeof(int32_t) * B, hipMemcpyHostToDevice)); }
+    HIPCHK(dAt.alloc(At.size())); HIPCHK(drs.alloc(m)); HIPCHK(dc.alloc(nc)); HIPCHK(db.alloc(nb));
+    HIPCHK(dobj.alloc(B)); HIPCHK(dx.alloc((size_t)B * n)); HIPCHK(dstatus.alloc(B)); HIPCHK(diters.alloc(B));
+    if (z) HIPCHK(dz.alloc((size_t)B * m));
+    if (relax) { HIPCHK(drelax.alloc(B)); HIPCHK(hipMemcpy(drelax, relax, sizeof(int32_t) * B, hipMemcpyHostToDevice)); }
     HIPCHK(hipMemcpy(dAt, At.data(), sizeof(double) * At.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(drs, rs.data(), sizeof(double) * m, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dc, c, sizeof(double) * nc, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b, sizeof(double) * nb, hipMemcpyHostToDevice));
     a.At = dAt; a.rs = drs; a.c = dc; a.b = db; a.relax = drelax;
+    a.obj = dobj; a.x = dx; a.z = dz; a.status = dstatus; a.iters = diters;
 
     const size_t lds = hmpc_lp_lds_bytes(n, m, a.a_in_lds);
     HIPCHK(hipFuncSetAttribute((const void *)hmpc_lp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
