@@ -18,9 +18,15 @@ states instead (x0 + 0.05 N(0,1) x_max per tree: 6 % of those nodes need the
 terminal set and are solved twice); ``--frontier-kind random_prefix`` is the
 random-binary generator of the same section (p = 0.5: 98 % infeasible, the easy
 mix; p = 0.1).  All of these, the hand-down variants and the other configs are
-secondary keys of the default run.
+secondary keys of a ``--full`` run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frontier B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frontier B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the steps, writes its outputs if asked and
+prints the headline line.  ``--full`` adds, after the timed steps, everything
+else the benchmark measures: the CPU baseline, the warm-start shift kernel, the
+secondary frontiers, the other configs, closed-loop MPC steps/s and the offline
+LPs (at N > 1: the strong-scaling frontier and the sharded closed loops).
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -633,11 +639,14 @@ def main():
     ap.add_argument('--frontier-total', type=int, default=0,
                     help='strong scaling: this many nodes IN TOTAL, split over the ranks (BASELINE configs[2]: 1024 over 8 GPUs); '
                          'overrides --frontier')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary frontiers / configs / closed-loop figures')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figures, everything else the benchmark measures: CPU baseline, warm-start shift kernel, '
+                         'secondary frontiers, other configs, closed-loop MPC steps/s, offline LPs (N > 1: strong scaling, sharded closed loops)')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary frontiers / configs / closed-loop figures')
     ap.add_argument('--workload', default='cart_pole_n20', choices=('cart_pole_n20', 'cart_pole_n40', 'random_mld'),
                     help='cart_pole_n20: the headline (BASELINE configs[1]/[2]); the others (configs[3], configs[4]) are for profiling '
-                         'their kernels with the same harness -- their numbers are secondary keys of the default run')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                         'their kernels with the same harness -- their numbers are secondary keys of a --full run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline (and with it the secondary figures of one GPU)')
     ap.add_argument('--rehearse-on-one-gpu', action='store_true',
                     help='N > 1 ranks all on cuda:0 with a gloo group: rehearses the multi-rank path on a one-GPU box '
                          '(the number it prints is not a scaling measurement)')
@@ -784,7 +793,7 @@ def main():
     # beside the weak default, in the same multi-GPU run: same step (solve the shard, all-reduce the incumbent), same
     # bracketing, max over the ranks
     strong = None
-    if world > 1 and args.frontier_total == 0 and args.workload == 'cart_pole_n20' and args.frontier_kind == 'real_tree' and 1024 % world == 0:
+    if args.full and world > 1 and args.frontier_total == 0 and args.workload == 'cart_pole_n20' and args.frontier_kind == 'real_tree' and 1024 % world == 0:
         xs_all, fs_all, _ = real_tree_frontier(ctrl, 1024, 0, load_fixture('cart_pole_with_walls')['x_max'], spread=spread)
         mine = shard(1024, world, rank)
         xs, fs = torch.from_numpy(np.ascontiguousarray(xs_all[mine])).to(dev), torch.from_numpy(np.ascontiguousarray(fs_all[mine])).to(dev)
@@ -816,7 +825,7 @@ def main():
     # 1024 loops in total, one fleet of 1024 / N loops per rank, disturbances seeded by the GLOBAL simulation index; same
     # bracketing as the QP metric (barrier + synchronize on both sides, max over the ranks), steps summed over the ranks.
     fleet_sharded = None
-    if world > 1 and args.workload == 'cart_pole_n20' and not args.no_secondary:
+    if args.full and world > 1 and args.workload == 'cart_pole_n20' and not args.no_secondary:
         fleet_sharded = sharded_fleet_rate(ctrl, world, rank, barrier, dist, dev)
 
     status = out['status'].cpu().numpy()
@@ -879,17 +888,17 @@ def main():
         if fleet_sharded is not None:
             line['mpc_steps_per_sec'] = {'fleet_sharded': fleet_sharded,
                                          'note': 'closed loop sigma=0.001, warm-started B&B, simulations sharded over the ranks (simulation s on rank s mod N), reference (published, Gurobi): 26.8 steps/s'}
-        if world == 1 and args.workload == 'cart_pole_n20':
+        if args.full and world == 1 and args.workload == 'cart_pole_n20':
             try:  # second kernel of the path (HBM bound), a few milliseconds
                 line['warm_start_shift'] = shift_bandwidth(ctrl, dev)
             except Exception as e:
                 line['warm_start_shift'] = {'error': str(e)}
         progress('timed region done: %.3f ms per step' % (1e3 * elapsed / args.steps))
-        if not args.no_cpu_baseline and args.workload != 'random_mld':
+        if args.full and not args.no_cpu_baseline and args.workload != 'random_mld':
             # (rank 0 only; at N > 1 the other ranks have finished their timed regions and wait in the final barrier)
             line['cpu_baseline'] = cpu_baseline(ctrl, x0_h, fix_h)
             progress('cpu baseline done')
-        if world == 1 and not args.no_secondary and not args.no_cpu_baseline and args.workload == 'cart_pole_n20':
+        if args.full and world == 1 and not args.no_secondary and not args.no_cpu_baseline and args.workload == 'cart_pole_n20':
             for key, fn in (('frontiers', lambda: secondary_frontiers(ctrl, dev, load_fixture('cart_pole_with_walls')['x_max'])), ('other_configs', lambda: other_configs(dev)),
                             ('mpc_steps_per_sec', lambda: mpc_steps_per_sec(ctrl)), ('offline_lps', offline_lps)):
                 try:

@@ -5,7 +5,7 @@ set -e -o pipefail
 TAG=${1:-ic}; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=$GRAFT_REPO_ROOT/gpurun_out
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-secondary"
 for L in "$@"; do
     export HMPC_LIBRARY_NAME=$L
     N=${L%.so}

@@ -6,7 +6,7 @@ set -e -o pipefail
 TAG=${1:-ab}; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=$GRAFT_REPO_ROOT/gpurun_out
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary $*"
+B="python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-secondary $*"
 for V in sized shipped; do
     if [ $V = shipped ]; then export HMPC_JIT_SIZED=0; fi
     rm -rf $O/${TAG}_${V}_*
