@@ -5,8 +5,10 @@ of the HIP kernel: the node QP of the reference (``warm_start_hmpc/controller.py
 as dense matrices, the active set is read from the multipliers of a record (``mu > 0``, ``nu > 0``,
 fixed binaries), and the equality-constrained QP on it is solved with numpy's SVD (particular solution
 + null-space minimisation).  Where the cost is strictly convex (the states, and the inputs the cost
-sees) the result is THE solution of the node if the record's active set is right -- which the KKT
-checkers of ``kkt_checks.py`` establish separately.
+sees) the result is THE solution of the node if the record's active set is right -- which the
+certificate establishes separately: ``certificates.assert_certified`` (the KKT checkers of
+``kkt_checks.py`` over every record) runs beside this check wherever ``test_gpu_parity._compare``
+is given the initial state, and on the handed-down records of ``test_handdown.py``.
 """
 import numpy as np
 

@@ -201,3 +201,32 @@ def real_tree_with_parents(ctrl, x0, leaves_too=False, **search):
             g[d - 1] = -1
             parent[i] = where.get(g.tobytes(), -1)
     return fix, parent
+
+
+def dive_leaf(qp, mld, x0, T, feasible=False):
+    """A dive to a leaf of a random MLD of random_mld: the binaries of stage t from the sign of c_j'x_t of the current relaxation,
+    solved on ``qp`` (feasible: every relaxation on the way must be).  int8 [T nub]."""
+    nx, nub, nuc = mld.nx, mld.nub, mld.nu - mld.nub
+    Cj = np.array([mld.F[2 * nx + 2 * nuc + 4 * j] for j in range(nub)])
+    leaf = np.full((1, T * nub), -1, np.int8)
+    for t in range(T):
+        r = qp.solve_batch(x0, leaf)
+        assert r['status'][0] == 0 or not feasible
+        leaf[0, t * nub:(t + 1) * nub] = (r['primal'][0][:(T + 1) * nx].reshape(T + 1, nx)[t] @ Cj.T >= 0)
+    return leaf[0]
+
+
+def dive_and_prefix_frontier(qp, mld, x0, T, seed, dives=96):
+    """The frontier the random MLDs of helpers.random_mld are tested on (the kernels compiled per problem): 64 random prefixes
+    (mostly infeasible) and ``dives`` prefixes of dive_leaf, every other one with one flipped binary.  int8 [64 + dives, T nub]."""
+    nub = mld.nub
+    leaf = dive_leaf(qp, mld, x0, T)[None]
+    rng = np.random.default_rng(seed)
+    fix = np.concatenate((random_prefix_frontier(T, nub, 64, p_one=0.3), np.full((dives, T * nub), -1, np.int8)))
+    for k in range(65, 64 + dives):
+        d = int(rng.integers(1, T * nub + 1))
+        fix[k, :d] = leaf[0, :d]
+        if k % 2 == 0:
+            j = int(rng.integers(0, d))
+            fix[k, j] = 1 - fix[k, j]
+    return fix

@@ -12,9 +12,10 @@ import os
 import numpy as np
 import pytest
 
-from helpers import make_controller, load_fixture, random_prefix_frontier, random_mld, _NoBackend, exercise_bounded_qp
+from helpers import make_controller, load_fixture, random_prefix_frontier, random_mld, dive_leaf, dive_and_prefix_frontier, _NoBackend, exercise_bounded_qp
 from dense_qp import determined_inputs
 from kkt_checks import check_solution, is_disjoint_cover
+from certificates import assert_certified, record_from_device, new_margins, margins_line
 from warm_start_hmpc_amd.subproblem_solution import SubproblemSolution
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +54,7 @@ def _rel(a, b, elementwise=True, efloor=None):
 
 
 _DENSE = {}
+MARGINS = new_margins()   # certificate residuals of the kernels' records beside the oracle's, over every _compare of this session
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -61,6 +63,7 @@ def _report_worst_deviations():
     line = ('parity margins of this run: kernel vs oracle norm-wise %.2e, element-wise (floor %.0e) %.2e; kernel vs dense '
             'active-set solve %.2e; unpolished records (interior-point iterates) norm-wise %.2e'
             % (WORST['norm'], EFLOOR, WORST['element'], WORST['dense'], WORST['iterate']))
+    line += '; ' + margins_line(MARGINS)
     print('\n' + line)
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     if os.path.isdir(out):
@@ -110,10 +113,13 @@ def _trajectories_close(ctrl, T, fix, pa, pb, what='', elementwise=True, efloor=
 
 def _compare(ctrl, a, b, T, fix=None, min_polished=1.0, x0=None, efloor=None):
     """a: records of the HIP path, b: of the oracle.  With x0 (and fix) the polished records of the HIP path are also
-    checked against the dense active-set solve, which shares no code with either."""
+    checked against the dense active-set solve, which shares no code with either, and EVERY record of the HIP path is held to
+    its own certificate (tests/certificates.py: KKT point or Farkas ray, from the rows as written out), the oracle's records of
+    the same workload being the reference."""
     assert np.array_equal(a['status'], b['status']), np.flatnonzero(a['status'] != b['status'])
     if x0 is not None and fix is not None:
         _dense_check(ctrl, T, x0, fix, a)
+        assert_certified(ctrl, x0, fix, a, ref=b, margins=MARGINS)
     assert np.all(a['status'] <= 1)
     fin = a['status'] == 0
     # polished on both sides (every optimal node of the cart-pole systems): vertex solutions, objectives to 1e-8;
@@ -225,6 +231,7 @@ def test_golden_vectors():
         np.testing.assert_allclose(res['obj'][fin], g[name + '_obj'][fin], rtol=1e-8, atol=1e-11)
         ref = np.hstack((g[name + '_x'], g[name + '_u']))
         _trajectories_close(ctrl, T, g[name + '_fix'][fin], res['primal'][fin], ref[fin], name)
+        assert_certified(ctrl, g[name + '_x0'], g[name + '_fix'], res, what=name)   # (no oracle record in the file: base tolerances)
         if name + '_bb_ub' not in g:
             continue
         # the whole branch and bound through the GPU path: binary assignment bit-exact, the incumbent's
@@ -377,19 +384,7 @@ def test_register_kernel_compiled_for_an_arbitrary_shape():
         ctrl = HybridModelPredictiveController(mld, T, objective, None, backend=_NoBackend())
         hip, orc = HipBatchedQP(ctrl.problem_data()), OracleBatchedQP(ctrl.problem_data(), threads=8)
         assert hip.kernel_info() == (6, 6, 6), hip.kernel_info()   # (compiled with the problem's sizes; 3: per shape, HMPC_JIT_SIZED=0)
-        Cj = np.array([mld.F[2 * nx + 2 * nuc + 4 * j] for j in range(nub)])
-        leaf = np.full((1, T * nub), -1, np.int8)
-        for t in range(T):
-            r = orc.solve_batch(x0, leaf)
-            leaf[0, t * nub:(t + 1) * nub] = (r['primal'][0][:(T + 1) * nx].reshape(T + 1, nx)[t] @ Cj.T >= 0)
-        rng = np.random.default_rng(seed)
-        fix = np.concatenate((random_prefix_frontier(T, nub, 64, p_one=0.3), np.full((96, T * nub), -1, np.int8)))
-        for k in range(65, 160):
-            d = int(rng.integers(1, T * nub + 1))
-            fix[k, :d] = leaf[0, :d]
-            if k % 2 == 0:
-                j = int(rng.integers(0, d))
-                fix[k, j] = 1 - fix[k, j]
+        fix = dive_and_prefix_frontier(orc, mld, x0, T, seed)
         for waves in ('1', '2', '4'):
             os.environ['HMPC_WAVES'] = waves
             try:
@@ -431,19 +426,7 @@ def test_sized_kernels_of_a_problem_beyond_the_static_row_map(which):
     finally:
         del os.environ['HMPC_JIT_SIZED']
     assert plain.kernel_info() == (0, 0, 0)
-    Cj = np.array([mld.F[2 * nx + 2 * nuc + 4 * j] for j in range(nub)])
-    leaf = np.full((1, T * nub), -1, np.int8)
-    for t in range(T):
-        r = orc.solve_batch(x0, leaf)
-        leaf[0, t * nub:(t + 1) * nub] = (r['primal'][0][:(T + 1) * nx].reshape(T + 1, nx)[t] @ Cj.T >= 0)
-    rng = np.random.default_rng(seed)
-    fix = np.concatenate((random_prefix_frontier(T, nub, 64, p_one=0.3), np.full((96, T * nub), -1, np.int8)))
-    for k in range(65, 160):
-        d = int(rng.integers(1, T * nub + 1))
-        fix[k, :d] = leaf[0, :d]
-        if k % 2 == 0:
-            j = int(rng.integers(0, d))
-            fix[k, j] = 1 - fix[k, j]
+    fix = dive_and_prefix_frontier(orc, mld, x0, T, seed)
     b = orc.solve_batch(x0, fix)
     assert (b['status'] == 0).sum() >= 20 and (b['status'] == 1).sum() >= 20
     for waves in ('1', '2', '4'):
@@ -523,7 +506,7 @@ def test_register_kernel_on_the_bench_workload_of_generic_vs_specialised():
             assert np.array_equal(r['status'], b['status']), (name, waves, np.flatnonzero(r['status'] != b['status']))
             assert np.all(r['polished'][r['status'] == 0] > 0), (name, waves, np.flatnonzero((r['status'] == 0) & (r['polished'] == 0)))
         _compare(ctrl, a, b, T, fix, min_polished=1.0, x0=x0, efloor=1e-5)
-        _compare(ctrl, g, b, T, fix, min_polished=1.0, efloor=1e-5)
+        _compare(ctrl, g, b, T, fix, min_polished=1.0, x0=x0, efloor=1e-5)
     assert spec.jit_stats() == (0, 0, 0)
 
 
@@ -564,7 +547,8 @@ def test_a_compiled_kernel_that_leaves_nodes_undecided_gets_a_second_opinion(mon
                    dual=torch.empty(1500, bad.qp.n_dual, dtype=torch.float64, device=dev))
         bad.qp.solve_batch_device(torch.from_numpy(x0).to(dev), torch.from_numpy(fix).to(dev), out)
         torch.cuda.synchronize()
-        st, obj, prim = out['status'].cpu().numpy(), out['obj'].cpu().numpy(), out['primal'].cpu().numpy()
+        got = record_from_device(*(out[k].cpu().numpy() for k in ('obj', 'dual_obj', 'status', 'iters', 'primal', 'dual')))
+        st, obj, prim = got['status'], got['obj'], got['primal']
     else:
         from warm_start_hmpc_amd.fleet import FleetMPC
         errors = load_fixture('reference_closed_loop')['errors_0003'][:3, :4]
@@ -578,6 +562,9 @@ def test_a_compiled_kernel_that_leaves_nodes_undecided_gets_a_second_opinion(mon
         fin = st == 0
         np.testing.assert_allclose(obj[fin], ref['obj'][fin], rtol=1e-9, atol=1e-12)
         np.testing.assert_allclose(prim[fin], ref['primal'][fin], rtol=0, atol=1e-7)
+        # the batch mixes records of two kernels (every fifth node is the shipped kernel's): each certifies itself, at the base tolerances
+        counts = assert_certified(bad, x0, fix, got, what='second opinion, %s entry' % entry)
+        assert counts['skipped'] == 0 and counts['polished'] + counts['unpolished'] == fin.sum()
     dropped, runs, agreed = bad.qp.jit_stats()                              # (takes the counts of the last call in)
     err = capfd.readouterr().err
     assert dropped >= 1 and runs >= 1 and agreed == 0, (dropped, runs, agreed)
@@ -725,17 +712,12 @@ def test_streaming_kernel_baseline_config4():
     # frontier: prefixes of a dive to a feasible leaf (binaries of stage t from the sign of c_j'x_t of the
     # current relaxation), every other one with one flipped binary -- random prefixes are all infeasible here
     nub, nx = 8, 20
-    Cj = np.array([mld.F[52 + 4 * j] for j in range(nub)])
-    leaf = np.full((1, T * nub), -1, np.int8)
-    for t in range(T):
-        r = orc.solve_batch(x0, leaf)
-        assert r['status'][0] == 0
-        leaf[0, t * nub:(t + 1) * nub] = (r['primal'][0][:(T + 1) * nx].reshape(T + 1, nx)[t] @ Cj.T >= 0)
+    leaf = dive_leaf(orc, mld, x0, T, feasible=True)
     # BASELINE's size: the 4096 DISTINCT nodes of the bench's dive frontier (bench.dive_frontier; until round 3: 256 nodes)
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from bench import dive_frontier
-    fix = dive_frontier(leaf[0], 4096, 0)
+    fix = dive_frontier(leaf, 4096, 0)
     orc.threads = os.cpu_count() or 8
     a, b = hip.solve_batch(x0, fix), orc.solve_batch(x0, fix)
     assert hip.launch_info()[1] > 100 * 1024          # the streaming carve: vectors only, still most of a CU
@@ -791,12 +773,7 @@ def test_streaming_kernel_other_shapes(monkeypatch, nx, nuc, nub, T, seed):
     count = 48
     fix = np.full((count, T * nub), -1, np.int8)
     if nub:
-        Cj = np.array([mld.F[2 * nx + 2 * nuc + 4 * j] for j in range(nub)])
-        leaf = np.full((1, T * nub), -1, np.int8)
-        for t in range(T):
-            r = orc.solve_batch(x0, leaf)
-            assert r['status'][0] == 0
-            leaf[0, t * nub:(t + 1) * nub] = (r['primal'][0][:(T + 1) * nx].reshape(T + 1, nx)[t] @ Cj.T >= 0)
+        leaf = dive_leaf(orc, mld, x0, T, feasible=True)[None]
         rng = np.random.default_rng(seed)
         for k in range(1, count):
             d = int(rng.integers(1, T * nub + 1))

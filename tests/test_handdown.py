@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import make_controller, real_tree_with_parents
+from certificates import assert_certified, record_from_device
 
 X0 = np.array([0., 0., 1., 0.])
 
@@ -85,6 +86,10 @@ def test_handed_down_active_sets_on_the_gpu(fixture, T):
     opt = cold['status'] == 0
     nxs = (T + 1) * hip.mld.nx
     assert np.max(np.abs(ow['primal'][opt][:, :nxs] - warm['primal'][opt][:, :nxs])) < 1e-6
+    # the handed-down records certify themselves (multipliers included: they become the next step's bounds), the oracle's
+    # records of the same hand-down being the reference; and so do the cold ones
+    assert_certified(hip, X0, fix, warm, ref=ow, what='handed down')
+    assert_certified(hip, X0, fix, cold, ref=oc, what='cold')
 
 
 @pytest.mark.gpu
@@ -108,6 +113,12 @@ def test_hand_down_in_the_device_pointer_form_and_in_the_tree_search():
     assert np.array_equal(out['status'].cpu().numpy(), host['status'])
     assert np.array_equal(out['iters'].cpu().numpy() & 0xFFFF, host['iters'])
     assert np.array_equal(out['obj'].cpu().numpy(), host['obj'])           # same records through both entry points
+    orc = make_controller('cart_pole_with_walls', backend='oracle', threads=8)
+    oc = orc.qp.solve_batch(X0, fix)
+    ow = orc.qp.solve_batch(X0, fix, warm=(oc['primal'], oc['dual'], index))     # (the oracle's records of the same hand-down)
+    assert_certified(hip, X0, fix, host, ref=ow, what='handed down, host entry')
+    assert_certified(hip, X0, fix, record_from_device(*(out[k].cpu().numpy() for k in ('obj', 'dual_obj', 'status', 'iters', 'primal', 'dual'))),
+                     ref=ow, what='handed down, device entry')
     # the tree search with the hand-down: same incumbent; the number of solves may move by a node or two (multipliers
     # of dependent active rows are not unique, a handed-down solve may return another optimal choice: child bounds
     # parent bound + multiplier then differ in the order equal bounds are met -- as between any two solvers)
@@ -158,4 +169,5 @@ def test_hand_down_on_the_streaming_kernel():
     both = opt & (a['polished'] > 0) & (b['polished'] > 0)
     xs = (T + 1) * nx
     assert np.abs(a['primal'][both][:, :xs] - b['primal'][both][:, :xs]).max() < 1e-7
+    assert_certified(ctrl, x0, f, a, ref=b, what='handed down, streaming kernel')
     assert a['iters'].mean() < cold_k['iters'].mean()
