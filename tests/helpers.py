@@ -44,6 +44,15 @@ def make_controller(name='cart_pole_with_walls', T=None, terminal=True, backend=
     return ctrl
 
 
+def long_head_parts():
+    """Cart-pole with walls, N = 10, the committed terminal set listed twice -- (F_T, h_T) and (F_T, 1.5 h_T) -- so that the
+    last stage has ncL = 28 + 2 x 102 = 232 rows (the warm-start shift's head of a row then exceeds one batch of 192).
+    Returns (mld, T, objective, terminal set)."""
+    d = load_fixture('cart_pole_with_walls')
+    mld = MLDSystem([d['A'], d['B']], [d['F'], d['G'], d['h']], int(d['nub']))
+    return mld, 10, [d['Q'], d['R'], d['Q_T']], [np.vstack((d['F_T'], d['F_T'])), np.concatenate((d['h_T'], 1.5 * d['h_T']))]
+
+
 def random_prefix_frontier(T, nub, count, p_one=0.5, seed0=1000):
     """Synthetic frontier of SURVEY.md 8(d) C2: node k (seed seed0+k) fixes the first d binaries
     in (t, i) order, d ~ U{0..T*nub}, to Bernoulli(p_one) values; the rest are free (-1)."""

@@ -10,7 +10,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conftest  # noqa: F401  (puts the package on the path)
-from helpers import random_mld, _NoBackend
+from helpers import random_mld, long_head_parts, _NoBackend
 
 # (nx, nuc, nub, seed, T): random MLDs of helpers.random_mld
 REGISTER_SHAPES = ((6, 2, 3, 3, 8), (6, 2, 3, 3, 12), (8, 3, 4, 2, 10), (8, 5, 2, 55, 12), (3, 3, 6, 38, 12),   # (the last two: the binaries round 4 saw come out wrong)
@@ -30,6 +30,13 @@ def problem(nx, nuc, nub, seed, T):
     return HybridModelPredictiveController(mld, T, objective, None, backend=_NoBackend()).problem_data(), mld, objective, x0
 
 
+def long_head_problem():
+    """The cart-pole whose last stage has 232 rows (helpers.long_head_parts; tests/test_shift.py)."""
+    from warm_start_hmpc_amd.controller import HybridModelPredictiveController
+    mld, T, objective, terminal = long_head_parts()
+    return HybridModelPredictiveController(mld, T, objective, terminal, backend=_NoBackend()).problem_data()
+
+
 def prewarm(verbose=False, prune=False):
     """prune: entries of the IN-TREE cache that none of these problems uses are deleted afterwards -- what an edit of the kernel
     sources leaves behind (the key holds a hash of the sources); the directory travels to the GPU boxes with the tree."""
@@ -42,6 +49,10 @@ def prewarm(verbose=False, prune=False):
         if verbose:
             print(spec, [os.path.basename(p) for p in got], flush=True)
         paths += got
+    got = jit_prebuild(long_head_problem())
+    if verbose:
+        print('long_head', [os.path.basename(p) for p in got], flush=True)
+    paths += got
     cache = os.path.join(os.path.dirname(LIBRARY_PATH), 'jit_cache')
     if prune and os.path.isdir(cache) and paths and all(os.path.dirname(q) == cache for q in paths):
         keep = set(os.path.basename(q) for q in paths)

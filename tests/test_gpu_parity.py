@@ -815,6 +815,16 @@ def test_lockstep_closed_loops_on_gpu():
         assert max(a['nodes_ws'][k][1:]) <= 60 and min(a['nodes_cs'][k]) >= 150
 
 
+def _shift_copied(ctrl):
+    """Columns of a shifted dual row that are copies or zeros: everything but mu'_{T-2} and rho'_{T-1} (tests/test_shift.py
+    holds those two to an extended-precision reference)."""
+    cut, T = ctrl.layout.dual_slices(), ctrl.T
+    copied = np.ones(ctrl.layout.n_dual, dtype=bool)
+    copied[cut['mu'][T - 2]] = False
+    copied[cut['rho'][T - 1]] = False
+    return copied
+
+
 def test_device_warm_start_shift_matches_host_forms():
     # SURVEY 8(f) rank 1: the node shift of controller.py:431-721 as one kernel launch over the leaves of
     # several trees, against (a) the vectorised numpy form and (b) the reference-shaped per-leaf Python form
@@ -839,6 +849,7 @@ def test_device_warm_start_shift_matches_host_forms():
         fin = np.isfinite(ref.lb)
         np.testing.assert_allclose(d.lb[fin], ref.lb[fin], rtol=1e-10, atol=1e-12)
         np.testing.assert_allclose(d.dual, ref.dual, rtol=1e-12, atol=1e-13)
+        np.testing.assert_array_equal(d.dual[:, _shift_copied(ctrl)], ref.dual[:, _shift_copied(ctrl)])   # copies and zeros: exact
         np.testing.assert_allclose(d.dobj, ref.dobj, rtol=1e-10, atol=1e-12)
         assert np.array_equal(d.has_dual, ref.has_dual)
         reopened += int((~d.has_dual).sum())
@@ -888,6 +899,7 @@ def test_both_shift_kernels_on_odd_shapes(monkeypatch, fixture, T, rows):
         fin = np.isfinite(ref.lb)
         np.testing.assert_allclose(d.lb[fin], ref.lb[fin], rtol=1e-10, atol=1e-12)
         np.testing.assert_allclose(d.dual, ref.dual, rtol=1e-12, atol=1e-13)
+        np.testing.assert_array_equal(d.dual[:, _shift_copied(ctrl)], ref.dual[:, _shift_copied(ctrl)])   # copies and zeros: exact
         np.testing.assert_allclose(d.dobj, ref.dobj, rtol=1e-10, atol=1e-12)
         assert np.array_equal(d.has_dual, ref.has_dual)
 
