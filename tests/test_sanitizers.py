@@ -4,10 +4,13 @@
     driven, in a child process with libasan preloaded, through everything the suites ask of it: cold solves with and
     without terminal set, the lazy second solve, the active-set polish with its tolerance escalation (random MLD), the
     parent -> child hand-down, infeasible nodes, OpenMP over nodes; the LP oracle on the terminal-set LPs;
-  * the fleet driver's host code -- the tree bookkeeping of csrc/hmpc_tree.h, shared with hmpc_fleet.hip -- compiled with
-    g++ -fsanitize=address,undefined into tests/host/tree_driver.cpp and driven by QP results of the CPU oracle through
-    the sequence of hmpc_fleet_solve / hmpc_fleet_shift (select, expand, consume, retain, adopt), with speculation, dive
-    prediction and hand-down; its costs, solve and leaf counts must be those of the Python branch and bound.
+  * the fleet driver's host code -- csrc/hmpc_tree.h: the bookkeeping of a tree and everything hmpc_fleet.hip does per
+    round, step and shift that needs no device -- compiled with g++ -fsanitize=address,undefined into
+    tests/host/tree_driver.cpp.  The driver restates none of it: it calls the functions hmpc_fleet_solve / hmpc_fleet_shift
+    call, in their order (select, count and fill a round, record its results, consume, close the step, retain, stage and
+    adopt the shift), with QP results of the CPU oracle in place of the launch, its flags translated to the C ABI's so that
+    weak and uncertified nodes arrive as in the library, with speculation, dive prediction and hand-down; its costs, solve
+    and leaf counts must be those of the Python branch and bound.
 Any report of either sanitizer fails the test (halt_on_error; stderr is searched as well)."""
 import json
 import os

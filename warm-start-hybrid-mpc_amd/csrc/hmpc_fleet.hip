@@ -16,6 +16,8 @@
 //     binaries' bounds (1.3 KB per node) through pinned staging, on one stream.
 // Semantics per tree are those of warm_start_hmpc_amd/batched.py (feedforward_many / construct_warm_start_many),
 // against which tests/test_fleet.py checks it step by step.
+// The host's share of a step is in hmpc_tree.h, free of HIP, where it runs under sanitizers (tests/host/tree_driver.cpp);
+// this file owns the buffers and does the copies, launches and synchronisations between those phases.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -25,11 +27,12 @@
 #include <unordered_map>
 #include <vector>
 
-#include "hmpc_tree.h" // FleetResult, FleetTree and the tree bookkeeping (host only, testable under sanitizers)
+#include "hmpc_tree.h" // FleetTree and the host logic of a round, a step and a shift (host only, testable under sanitizers)
 
 struct hmpc_fleet {
     hmpc_handle *h = nullptr;
     int K = 0;
+    FleetDims dims{};
     std::vector<FleetTree> trees;
     hipStream_t stream = nullptr; // (destroyed after the buffers below are released: hmpc_fleet_destroy)
     DevBuf<double> pool[2], dobj[2]; // rows: dobj[s].size()
@@ -78,11 +81,36 @@ int fleet_fail(hmpc_fleet *f, int code, const std::string &msg)
     return fail(code, msg + " -- the fleet must be reset (hmpc_fleet_reset(f, -1)) before it is used again");
 }
 
+// A call that returns before it is done leaves the fleet broken.
+struct BrokenUnlessDone {
+    hmpc_fleet *f;
+    bool ok = false;
+    ~BrokenUnlessDone() { if (!ok) f->broken = true; }
+};
+
+// Host wall time by phase (hmpc_fleet_timing): from construction, or the last next(), to the next next() or the end of the
+// scope goes to the slot named last.
+struct Phase {
+    double *slot;
+    double t0 = now();
+    explicit Phase(double &s) : slot(&s) {}
+    Phase(const Phase &) = delete;
+    ~Phase() { *slot += now() - t0; }
+    void next(double &s)
+    {
+        const double t = now();
+        *slot += t - t0;
+        slot = &s;
+        t0 = t;
+    }
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+};
+
 // Room in the round buffers for B nodes: one that is short is replaced by room for max(2B, 1024) nodes.
 int fleet_ensure_round(hmpc_fleet *f, size_t B)
 {
     const DevProb &p = f->h->dp;
-    const size_t cap = std::max<size_t>(2 * B, 1024), nfix = (size_t)p.T * p.nub;
+    const size_t cap = std::max<size_t>(2 * B, 1024), nfix = (size_t)f->dims.nfix;
     hipError_t e = hipSuccess;
     auto grow = [&](auto &buf, size_t per_node) { if (e == hipSuccess) e = buf.grow(B * per_node, cap * per_node, f->stream); };
     grow(f->d_fix, nfix); grow(f->h_fix, nfix); grow(f->d_fix_out, nfix);
@@ -126,9 +154,11 @@ extern "C" int hmpc_fleet_create(hmpc_handle *h, int32_t K, hmpc_fleet **out)
     f->h = h;
     f->K = K;
     const DevProb &p = h->dp;
+    f->dims = fleet_dims(p.nx, p.nu, p.nub, p.T, p.nc, p.ncL, p.nq, p.nr, p.nqT);
+    if (f->dims.n_primal != p.n_primal || f->dims.n_dual != p.n_dual) return fail(HMPC_EINVAL, "fleet: the record sizes of hmpc_tree.h are not the handle's");
     f->trees.resize(K);
     for (auto &t : f->trees) {
-        tree_reset_cold(t, p.T * p.nub);
+        tree_reset_cold(t, f->dims.nfix);
         t.x0.assign(p.nx, 0.0);
     }
     const bool ok = f->d_kx0.alloc((size_t)K * p.nx) == hipSuccess && f->d_ku0.alloc((size_t)K * p.nu) == hipSuccess &&
@@ -156,8 +186,7 @@ extern "C" int hmpc_fleet_destroy(hmpc_fleet *f)
 extern "C" int hmpc_fleet_reset(hmpc_fleet *f, int32_t k)
 {
     if (!f || k < -1 || k >= f->K) return fail(HMPC_EINVAL, "fleet: bad loop index");
-    const int nfix = f->h->dp.T * f->h->dp.nub;
-    for (int i = (k < 0 ? 0 : k); i < (k < 0 ? f->K : k + 1); i++) tree_reset_cold(f->trees[i], nfix);
+    for (int i = (k < 0 ? 0 : k); i < (k < 0 ? f->K : k + 1); i++) tree_reset_cold(f->trees[i], f->dims.nfix);
     if (k < 0) f->broken = false;
     return HMPC_OK;
 }
@@ -167,7 +196,7 @@ extern "C" int hmpc_fleet_reset(hmpc_fleet *f, int32_t k)
 extern "C" int hmpc_fleet_stop(hmpc_fleet *f, int32_t k)
 {
     if (!f || k < 0 || k >= f->K) return fail(HMPC_EINVAL, "fleet: bad loop index");
-    tree_reset_cold(f->trees[k], f->h->dp.T * f->h->dp.nub);
+    tree_reset_cold(f->trees[k], f->dims.nfix);
     f->trees[k].running = false;
     return HMPC_OK;
 }
@@ -194,7 +223,7 @@ extern "C" int hmpc_fleet_solve(hmpc_fleet *f, const double *x0, int32_t width, 
     g_err.clear();
     if (!f || !x0) return fail(HMPC_EINVAL, "fleet: null argument");
     if (f->broken) return fail(HMPC_EINVAL, "fleet: an earlier call failed midway; reset the fleet (hmpc_fleet_reset(f, -1)) first");
-    struct Guard { hmpc_fleet *f; bool ok = false; ~Guard() { if (!ok) f->broken = true; } } guard{f};
+    BrokenUnlessDone guard{f};
     if (width < 1) width = 1;
     // speculation < 0: DIVE PREDICTION (for few loops: it fetches the primal rows of every round).  A branch-and-bound dive
     // follows the relaxation: where a parent's relaxed binaries round to, its descendants' mostly stay.  With a picked node
@@ -203,79 +232,41 @@ extern "C" int hmpc_fleet_solve(hmpc_fleet *f, const double *x0, int32_t width, 
     // in the depth where the subtree expansion (speculation > 0) is exponential.  Results wait in the cache and are consumed
     // only if and when the search selects those nodes: incumbent, leaves and solve counts are those of the search without it.
     // A cold start is then the root, one launch with the predicted dive, and what the prediction missed.
-    const bool dive = speculation < 0;
-    if (speculation < 0) speculation = 0;
+    FleetExpansion ex{std::max(speculation, 0), speculation < 0, f->handdown != 0, {}, {}};
     hmpc_handle *h = f->h;
     HIPCHK(hipSetDevice(h->device));
-    const DevProb &p = h->dp;
-    const int K = f->K, nfix = p.T * p.nub, nx = p.nx, nu = p.nu;
-    const int o_lb = (p.T + 1) * nx + (p.T - 1) * p.nc + p.ncL; // nu_lb then nu_ub, contiguous in the dual row
-    const double inf = std::numeric_limits<double>::infinity();
+    const FleetDims &d = f->dims;
+    const int K = f->K, nfix = d.nfix, nx = d.nx;
     for (int k = 0; k < K; k++) tree_begin_step(f->trees[k], x0 + (size_t)k * nx, nx);
-    {
-        // Rows nobody references are reclaimed: when every tree is cold (no node carries a row of its own or of its parent)
-        // the pools start from zero again.  Without this a fleet that is reset and solved at every step, never shifted --
-        // the cold searches of fleet.closed_loop_study -- kept every row ever written: 880 k rows of ~8 KB over the
-        // published sd = .01 study, 25-30 GB with the spare pool and the regrow copies (only hmpc_fleet_shift compacted).
-        bool cold = true;
-        for (int k = 0; k < K && cold; k++) {
-            const FleetTree &t = f->trees[k];
-            for (int i = 0; i < t.n && cold; i++) cold = t.row[i] < 0 && t.wrow[i] < 0;
-        }
-        if (cold) f->used = 0;
-    }
+    if (fleet_pools_idle(f->trees)) f->used = 0;
     std::vector<std::vector<int>> picks(K);
-    std::vector<int> order;
-    struct Launch { int k, depth; };
-    std::vector<Launch> launch;
-    std::vector<int8_t> level, next; // identifiers of one level of a speculative expansion
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    std::vector<FleetLaunch> launch;
+    std::vector<int32_t> weak;
     for (;;) {
         // candidates of every tree: alive, bound below the incumbent; the `width` smallest bounds, first wins ties
-        double t0 = now();
+        Phase phase(f->t_select);
         size_t npick = 0;
         for (int k = 0; k < K; k++) {
             tree_select(f->trees[k], width, tol, picks[k]);
             npick += picks[k].size();
         }
-        f->t_select += now() - t0;
         if (npick == 0) break;
-        t0 = now();
-        // what has to be launched: picked nodes without a cached result, and their speculative descendants
-        launch.clear();
-        size_t B = 0;
-        int rc;
-        bool any_warm = false;
-        for (int pass = 0; pass < 2; pass++) { // pass 0 counts, pass 1 fills the staging buffers
-            if (pass == 1) {
-                if (B == 0) break;
-                if ((rc = fleet_ensure_round(f, B))) return rc;
-                if ((rc = fleet_ensure_rows(f, f->used + B))) return rc;
-            }
-            size_t b = 0;
-            for (int k = 0; k < K; k++) {
-                FleetTree &t = f->trees[k];
-                for (int i : picks[k])
-                    tree_expand(t, i, nfix, speculation, dive, f->handdown != 0, level, next, [&](const int8_t *row, int depth, int32_t widx) {
-                        if (pass == 1) {
-                            std::memcpy(f->h_fix + b * nfix, row, nfix);
-                            std::memcpy(f->h_x0 + b * nx, t.x0.data(), nx * sizeof(double));
-                            f->h_widx[b] = widx;
-                            any_warm |= widx >= 0;
-                            launch.push_back({k, depth});
-                        }
-                        b++;
-                    });
-            }
-            B = b;
+        // what has to be launched: picked nodes without a cached result, and what rides along with them
+        phase.next(f->t_stage);
+        const size_t B = fleet_count_round(f->trees, picks, d, ex);
+        int rc, any_warm = 0;
+        if (B > 0) {
+            if ((rc = fleet_ensure_round(f, B))) return rc;
+            if ((rc = fleet_ensure_rows(f, f->used + B))) return rc;
+            any_warm = fleet_fill_round(f->trees, picks, d, ex, B, f->h_fix, f->h_x0, f->h_widx, launch);
+            if (any_warm < 0) return fleet_fail(f, HMPC_EDEVICE, "fleet: the two passes over a round's nodes disagree on their number");
         }
-        f->t_stage += now() - t0;
-        t0 = now();
+        phase.next(B > 0 ? f->t_device : f->t_consume);
         if (B > 0) {
             HIPCHK(hipMemcpyAsync(f->d_fix, f->h_fix, B * nfix, hipMemcpyHostToDevice, f->stream));
             HIPCHK(hipMemcpyAsync(f->d_x0, f->h_x0, B * nx * sizeof(double), hipMemcpyHostToDevice, f->stream));
-            double *rows = f->pool[f->cur] + f->used * p.n_dual;
-            hmpc_result r{f->d_obj, f->dobj[f->cur] + f->used, f->d_status, f->d_iters, f->ppool + f->used * p.n_primal, rows};
+            double *rows = f->pool[f->cur] + f->used * d.n_dual;
+            hmpc_result r{f->d_obj, f->dobj[f->cur] + f->used, f->d_status, f->d_iters, f->ppool + f->used * d.n_primal, rows};
             // (the parents' rows lie below f->used, this launch writes from f->used on)
             hmpc_warm hw{f->ppool, f->pool[f->cur], f->d_widx, (int32_t)f->used};
             if (any_warm) HIPCHK(hipMemcpyAsync(f->d_widx, f->h_widx, B * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
@@ -283,89 +274,49 @@ extern "C" int hmpc_fleet_solve(hmpc_fleet *f, const double *x0, int32_t width, 
             HIPCHK(hipMemcpyAsync(f->h_obj, f->d_obj, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
             HIPCHK(hipMemcpyAsync(f->h_status, f->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
             HIPCHK(hipMemcpyAsync(f->h_iters, f->d_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-            if (dive) { // the round's primal rows: the rounded binaries of its vertex nodes predict their descendants' dives
-                if (f->h_bits.grow(B * p.n_primal, 2 * B * p.n_primal, f->stream) != hipSuccess)
+            if (ex.dive) { // the round's primal rows: the rounded binaries of its vertex nodes predict their descendants' dives
+                if (f->h_bits.grow(B * d.n_primal, 2 * B * d.n_primal, f->stream) != hipSuccess)
                     return fail(HMPC_EDEVICE, "fleet: cannot allocate the prediction buffer");
-                HIPCHK(hipMemcpyAsync(f->h_bits, f->ppool + f->used * p.n_primal, B * p.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+                HIPCHK(hipMemcpyAsync(f->h_bits, f->ppool + f->used * d.n_primal, B * d.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
             }
-            HIPCHK(hipMemcpy2DAsync(f->h_nu, 2 * nfix * sizeof(double), rows + o_lb, p.n_dual * sizeof(double), 2 * nfix * sizeof(double), B,
+            HIPCHK(hipMemcpy2DAsync(f->h_nu, 2 * nfix * sizeof(double), rows + d.o_lb, d.n_dual * sizeof(double), 2 * nfix * sizeof(double), B,
                                     hipMemcpyDeviceToHost, f->stream));
             HIPCHK(hipStreamSynchronize(f->stream));
-            f->t_device += now() - t0;
-            t0 = now();
+            phase.next(f->t_consume);
             f->rounds++;
             f->launched += (long long)B;
-            for (size_t q = 0; q < B; q++) {
-                if (f->h_iters[q] & HMPC_ITERS_WEAK) {
-                    // infeasible, but the ray is no proof to tolerance: it prunes this node at this step only.  With a
-                    // dual objective of -inf the shift reopens the leaf whatever the model error (controller.py:555-558).
-                    const double ninf = -inf;
-                    HIPCHK(hipMemcpy(f->dobj[f->cur] + f->used + q, &ninf, sizeof(double), hipMemcpyHostToDevice));
-                }
-                const int d = launch[q].depth;
-                const double *nu_ = f->h_nu + q * 2 * nfix;
-                FleetResult e{f->h_obj[q], d < nfix ? nu_[d] : 0.0, d < nfix ? nu_[nfix + d] : 0.0, (int32_t)(f->used + q),
-                              f->h_status[q] == HMPC_OPTIMAL && (f->h_iters[q] & HMPC_ITERS_POLISHED) != 0, f->h_status[q] > 1,
-                              (f->h_iters[q] & HMPC_ITERS_UNCERTIFIED) != 0};
-                f->handed += (f->h_iters[q] & HMPC_ITERS_HANDED) != 0;
-                if (dive && e.vertex && d < nfix) {
-                    std::vector<int8_t> bits(nfix);
-                    const double *u = f->h_bits + q * p.n_primal + (size_t)(p.T + 1) * nx;
-                    for (int j = 0; j < nfix; j++) bits[j] = u[(j / p.nub) * nu + p.nuc + (j % p.nub)] > 0.5 ? 1 : 0;
-                    f->trees[launch[q].k].rounded.emplace(e.row, std::move(bits));
-                }
-                f->trees[launch[q].k].cache.emplace(tree_key(f->h_fix + q * nfix, d), e);
+            weak.clear();
+            f->handed += fleet_record_round(f->trees, launch, d, (int32_t)f->used, B, f->h_fix, f->h_obj, f->h_status, f->h_iters, f->h_nu, 2 * (size_t)nfix,
+                                            ex.dive ? (const double *)f->h_bits : nullptr, d.n_primal, weak);
+            for (int32_t q : weak) { // (infeasible, but the ray is no proof to tolerance: the shift must reopen the leaf)
+                const double ninf = -std::numeric_limits<double>::infinity();
+                HIPCHK(hipMemcpy(f->dobj[f->cur] + f->used + q, &ninf, sizeof(double), hipMemcpyHostToDevice));
             }
             f->used += B;
         }
         // prune / incumbent / branch, node by node in selection order (branch_and_bound.py:476-489)
-        struct Tick { double &acc; double t0; ~Tick() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; } } tick{f->t_consume, t0};
         for (int k = 0; k < K; k++) {
             const int bad = tree_consume(f->trees[k], picks[k], nfix, tol);
             if (bad == 1) return fail(HMPC_EDEVICE, "fleet: a selected node has no result");
             if (bad == 2) return fleet_fail(f, HMPC_EDEVICE, "fleet: the QP solver did not converge on a node (status MAXITER / NUMERICAL)");
         }
     }
-    for (int k = 0; k < K; k++) { // prunes without a certificate (HMPC_ITERS_UNCERTIFIED): counted; said aloud where a search's result rests on one
-        FleetTree &t = f->trees[k];
-        if (!t.uncertified) continue;
-        f->uncertified += t.uncertified;
-        if (t.unc_lb < t.ub) {
-            if (!f->resting)
-                fprintf(stderr, "hmpc: a branch-and-bound search pruned a node on the collapse of tau alone (no infeasibility certificate, HMPC_ITERS_UNCERTIFIED) "
-                                "whose bound %.6g lay below the final incumbent %.6g: the returned optimum rests on that prune (hmpc_fleet_uncertified counts further ones)\n",
-                        t.unc_lb, t.ub);
-            f->resting++;
-        }
-        t.uncertified = 0;
+    // the incumbents' primal rows: one gather launch, one copy
+    if (fleet_incumbent_rows(f->trees, f->h_inc)) {
+        HIPCHK(hipMemcpyAsync(f->d_inc, f->h_inc, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+        hipLaunchKernelGGL(hmpc_gather_rows, dim3(K), dim3(256), 0, f->stream, (const double *)f->ppool, (const int32_t *)f->d_inc, d.n_primal, f->d_prow);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(f->h_prow, f->d_prow, (size_t)K * d.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));
     }
-    {   // the incumbents' primal rows: one gather launch, one copy
-        bool any = false;
-        for (int k = 0; k < K; k++) {
-            f->h_inc[k] = (f->trees[k].running && f->trees[k].inc >= 0) ? f->trees[k].inc_row : -1;
-            any |= f->h_inc[k] >= 0;
-        }
-        if (any) {
-            HIPCHK(hipMemcpyAsync(f->d_inc, f->h_inc, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
-            hipLaunchKernelGGL(hmpc_gather_rows, dim3(K), dim3(256), 0, f->stream, (const double *)f->ppool, (const int32_t *)f->d_inc, p.n_primal, f->d_prow);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(f->h_prow, f->d_prow, (size_t)K * p.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipStreamSynchronize(f->stream));
-            for (int k = 0; k < K; k++)
-                if (f->h_inc[k] >= 0) f->trees[k].primal.assign(f->h_prow + (size_t)k * p.n_primal, f->h_prow + (size_t)(k + 1) * p.n_primal);
-        }
-    }
-    for (int k = 0; k < K; k++) {
-        FleetTree &t = f->trees[k];
-        t.cache.clear();
-        if (cost) cost[k] = t.running ? t.ub : inf;
-        if (solves) solves[k] = t.solves;
-        if (n_leaves) n_leaves[k] = t.running ? tree_leaves(t) : 0;
-        const bool ok = t.running && t.inc >= 0;
-        for (int j = 0; j < nu && u0; j++) u0[(size_t)k * nu + j] = ok ? t.primal[(size_t)(p.T + 1) * nx + j] : NAN;
-        for (int j = 0; j < nx && x1; j++) x1[(size_t)k * nx + j] = ok ? t.primal[nx + j] : NAN;
-        if (t.running && t.inc < 0) t.running = false; // infeasible MIQP: the loop ends here (statistical_analysis.py:99-108)
-    }
+    // prunes without a certificate (HMPC_ITERS_UNCERTIFIED): counted; said aloud where a search's result rests on one
+    const FleetUncertified unc = fleet_close_step(f->trees, d, f->h_inc, f->h_prow, cost, u0, x1, solves, n_leaves);
+    if (unc.resting && !f->resting)
+        fprintf(stderr, "hmpc: a branch-and-bound search pruned a node on the collapse of tau alone (no infeasibility certificate, HMPC_ITERS_UNCERTIFIED) "
+                        "whose bound %.6g lay below the final incumbent %.6g: the returned optimum rests on that prune (hmpc_fleet_uncertified counts further ones)\n",
+                unc.unc_lb, unc.ub);
+    f->uncertified += unc.pruned;
+    f->resting += unc.resting;
     guard.ok = true;
     return HMPC_OK;
 }
@@ -377,48 +328,26 @@ extern "C" int hmpc_fleet_shift(hmpc_fleet *f, const double *e0, int32_t *cover,
     g_err.clear();
     if (!f || !e0) return fail(HMPC_EINVAL, "fleet: null argument");
     if (f->broken) return fail(HMPC_EINVAL, "fleet: an earlier call failed midway; reset the fleet (hmpc_fleet_reset(f, -1)) first");
-    struct Guard { hmpc_fleet *f; bool ok = false; ~Guard() { if (!ok) f->broken = true; } } guard{f};
-    struct Tick { double &acc; double t0; ~Tick() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; } }
-        tick{f->t_shift, std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count()};
+    BrokenUnlessDone guard{f};
+    Phase phase(f->t_shift);
     hmpc_handle *h = f->h;
     HIPCHK(hipSetDevice(h->device));
-    const DevProb &p = h->dp;
-    const int K = f->K, nfix = p.T * p.nub, nx = p.nx, nu = p.nu, nub = p.nub, nuc = p.nuc;
+    const FleetDims &d = f->dims;
+    const int K = f->K, nx = d.nx, nu = d.nu;
     // kept leaves of all trees
     std::vector<std::vector<int>> keep(K);
-    size_t B = 0;
-    for (int k = 0; k < K; k++) {
-        FleetTree &t = f->trees[k];
-        if (cover) cover[k] = 0;
-        if (reopened) reopened[k] = 0;
-        if (!t.running || t.inc < 0) continue;
-        tree_retain(t, t.primal.data() + (size_t)(p.T + 1) * nx, nuc, nub, nfix, keep[k]);
-        B += keep[k].size();
-    }
+    const size_t B = fleet_retain_leaves(f->trees, d, keep, cover, reopened);
     if (B == 0) { guard.ok = true; return HMPC_OK; }
     int rc = fleet_ensure_round(f, B);
     if (rc) return rc;
     if ((rc = fleet_ensure_rows(f, std::max(f->used, B)))) return rc;
     double *hx = f->h_k, *hu = hx + (size_t)K * nx, *he = hu + (size_t)K * nu;
-    size_t b = 0;
-    for (int k = 0; k < K; k++) {
-        FleetTree &t = f->trees[k];
-        std::memcpy(hx + (size_t)k * nx, t.x0.data(), nx * sizeof(double));
-        std::memcpy(he + (size_t)k * nx, e0 + (size_t)k * nx, nx * sizeof(double));
-        for (int j = 0; j < nu; j++) hu[(size_t)k * nu + j] = keep[k].empty() ? 0.0 : t.primal[(size_t)(p.T + 1) * nx + j];
-        for (int i : keep[k]) {
-            if (t.row[i] < 0) return fail(HMPC_EINVAL, "fleet: a leaf carries no multipliers (unsolved root?)");
-            std::memcpy(f->h_fix + b * nfix, t.fix.data() + (size_t)i * nfix, nfix);
-            f->h_owner[b] = k;
-            f->h_src[b] = t.row[i];
-            f->h_lb[b] = t.lb[i];
-            b++;
-        }
-    }
+    if (!fleet_stage_shift(f->trees, d, keep, e0, hx, hu, he, f->h_fix, f->h_owner, f->h_src, f->h_lb))
+        return fail(HMPC_EINVAL, "fleet: a leaf carries no multipliers (unsolved root?)");
     HIPCHK(hipMemcpyAsync(f->d_kx0, hx, (size_t)K * nx * sizeof(double), hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->d_ku0, hu, (size_t)K * nu * sizeof(double), hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->d_ke0, he, (size_t)K * nx * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(hipMemcpyAsync(f->d_fix, f->h_fix, B * nfix, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->d_fix, f->h_fix, B * d.nfix, hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->d_owner, f->h_owner, B * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->d_src, f->h_src, B * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->d_lb, f->h_lb, B * sizeof(double), hipMemcpyHostToDevice, f->stream));
@@ -430,18 +359,8 @@ extern "C" int hmpc_fleet_shift(hmpc_fleet *f, const double *e0, int32_t *cover,
     HIPCHK(hipMemcpyAsync(f->h_flags, f->d_flags, B, hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     // the shifted leaves are the next tree: identifiers move one stage towards the present
-    b = 0;
-    for (int k = 0; k < K; k++) {
-        FleetTree &t = f->trees[k];
-        if (keep[k].empty()) continue;
-        const size_t n = keep[k].size();
-        for (size_t j = 0; j < n; j++)
-            if (!(f->h_flags[b + j] & 1)) return fail(HMPC_EDEVICE, "fleet: host and device disagree on the retain rule");
-        const int reop = tree_adopt_shifted(t, keep[k], f->h_lb + b, f->h_flags + b, (int32_t)b, nub, nfix);
-        b += n;
-        if (cover) cover[k] = (int32_t)n;
-        if (reopened) reopened[k] = reop;
-    }
+    if (!fleet_adopt_shift(f->trees, d, keep, f->h_lb, f->h_flags, cover, reopened))
+        return fail(HMPC_EDEVICE, "fleet: host and device disagree on the retain rule");
     f->cur = nxt;
     f->used = B;
     guard.ok = true;
