@@ -199,6 +199,63 @@ int hmpc_shift_batch_device(hmpc_handle *h, int32_t B, int32_t K, const int32_t 
                             const double *d_dual, const double *d_dual_obj, int8_t *d_fix_out, double *d_lb_out,
                             double *d_dual_out, double *d_dual_obj_out, uint8_t *d_flags, void *stream);
 
+/* ---- Certificates of a batch of records (KKT point / Farkas ray) ------------------------------------------
+ * Every record of hmpc_result carries its own certificate: an OPTIMAL node is a KKT point, an INFEASIBLE node a Farkas
+ * ray.  These entries evaluate it on the device, one wavefront per record (csrc/hmpc_certify.hip), from the rows AS
+ * WRITTEN OUT and the problem's UNSCALED matrices, in float64 -- nothing the solver computed for itself is trusted, obj
+ * and dual_obj included.  The conditions are the reference's three checkers (warm_start_hmpc/test/cart_pole_with_wall.py:
+ * 171-268: primal feasibility, dual feasibility = stationarity + sign, dual objective), scaled as tests/kkt_checks.py
+ * check_solution scales them; column by column the residuals are those of tests/certificates.py residuals():
+ *   stationarity      max |gradient of the Lagrangian in x_t, u_t|          / (1 + max(|lam|_inf, |mu|_inf))
+ *   sign              most negative of mu, nu_lb, nu_ub (0 if none)         / (1 + max(|lam|_inf, |mu|_inf))
+ *   dual_obj          |dual objective of the multipliers - dual_obj| / (1 + |dual objective of the multipliers|)
+ *   primal_equality   max |x_0 - x0|, |A x_t + B u_t - x_{t+1}|
+ *   primal_inequality largest violation of [F G] rows, terminal rows and the bounds of the binaries under `fix`
+ *   obj, gap          |cost of the primal row - obj|, |cost of the primal row - dual objective|, / (1 + |cost|)
+ *   ray_quadratic     max |rho|, |sigma| beside a ray        (EXACT: must be 0)
+ *   ray_objective     0 if the ray's dual objective is > 0, +inf otherwise (EXACT)
+ *   ray_primal        non-NaN entries of the primal row, + 1 for an obj that is not +inf (EXACT)
+ * A NaN anywhere in the rows of a decided record ends as a NaN residual, and NaN fails. */
+/* columns of the residual matrix, in this order; NaN where a column does not apply to the record's status */
+#define HMPC_CERT_STATIONARITY      0
+#define HMPC_CERT_SIGN              1
+#define HMPC_CERT_DUAL_OBJ          2
+#define HMPC_CERT_PRIMAL_EQUALITY   3   /* status 0 only */
+#define HMPC_CERT_PRIMAL_INEQUALITY 4   /* status 0 only */
+#define HMPC_CERT_OBJ               5   /* status 0 only */
+#define HMPC_CERT_GAP               6   /* status 0 only */
+#define HMPC_CERT_RAY_QUADRATIC     7   /* status 1 only */
+#define HMPC_CERT_RAY_OBJECTIVE     8   /* status 1 only: 0 or +inf */
+#define HMPC_CERT_RAY_PRIMAL        9   /* status 1 only */
+#define HMPC_CERT_COUNT            10
+
+/* verdict[b]: low byte = class (0 polished: OPTIMAL with HMPC_ITERS_POLISHED -- a handed-down record is one --, 1 unpolished,
+ * 2 infeasible, 3 weak: INFEASIBLE with HMPC_ITERS_WEAK, 4 skipped: status > 1, all residuals NaN, never failed);
+ * HMPC_CERT_FAILED set when a residual of the class's list exceeds its tolerance or is NaN (the EXACT columns: is not 0; a weak
+ * ray is exempt from the stationarity bound, and from that only);
+ * bits 16.. = mask of the failing columns */
+#define HMPC_CERT_FAILED 0x100
+
+/* One tolerance per class.  An argument and not a constant: the defaults are the bounds the project's own records are held
+ * to, but a VALID polished record can exceed 1e-8 -- the polish verifies rows on their unit form, and an inactive row of
+ * large norm (cart-pole systems at N = 40: norms 51 and 273) shows a primal inequality of 1.5e-8 .. 1.1e-7 and a gap of
+ * 1.9e-7 (tests/test_certificates.py); a caller with such rows widens `polished`. */
+typedef struct hmpc_cert_tol { double polished, unpolished, infeasible, weak; } hmpc_cert_tol; /* NULL: 1e-8, 5e-6, 1e-6, 1e-6 */
+
+/* Certifies B records.  x0, x0_stride, fix: as for hmpc_solve_batch (fix may be NULL for a problem without binaries);
+ * records: all six members required, B rows each (e.g. what hmpc_solve_batch filled).  residuals: B x HMPC_CERT_COUNT.
+ * Any problem hmpc_create admits can be certified: the matrices are staged in LDS where they fit and read in place where
+ * they do not.  Host-pointer form: copies in, runs, copies out, returns when done. */
+int hmpc_certify_batch(hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B,
+                       const hmpc_result *records, const hmpc_cert_tol *tol /* nullable */,
+                       double *residuals /* B x HMPC_CERT_COUNT */, int32_t *verdict /* B, nullable */);
+/* Device-pointer form: every pointer except tol is device memory; asynchronous on `stream`.  It allocates nothing, never
+ * synchronises and uses no workspace of the handle (hmpc_create keeps a copy of the unscaled matrices on the device), so
+ * hmpc_solve_batch_device followed by this call on the same stream certifies a frontier without a host round trip. */
+int hmpc_certify_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_stride, const int8_t *d_fix, int32_t B,
+                              const hmpc_result *d_records, const hmpc_cert_tol *tol /* nullable, host */,
+                              double *d_residuals, int32_t *d_verdict /* nullable */, void *stream);
+
 /* ---- Closed loops in lockstep ("fleet") ---------------------------------------------------------------
  * K independent closed loops of the controller advanced together -- the shape of the reference's Monte-Carlo
  * study (notebooks/cart_pole_with_walls/statistical_analysis.py:93-196: per step one warm-started branch and

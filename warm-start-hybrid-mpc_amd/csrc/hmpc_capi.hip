@@ -21,6 +21,7 @@
 #include "hmpc_kernel.hip" // one translation unit: the kernels are launched from this file
 #include "hmpc_jit.h"      // register kernels for shapes without a built-in instantiation, compiled at hmpc_create
 #include "hmpc_shift.hip"
+#include "hmpc_certify.hip" // certificates of a batch of records (hmpc_certify_batch)
 
 #define HMPC_CHECK_NODES 64 // (even) nodes of the first-use check of a kernel compiled at hmpc_create (hmpc_check_compiled)
 static thread_local std::string g_err;
@@ -121,6 +122,10 @@ struct hmpc_handle {
     DevBuf<int32_t> pend;  // two-launch form of the lazy terminal set: [0] how many nodes wait for their second solve, [1 ..] which
     DevBuf<char> d_shift;  // staging of the host-pointer shift
     DevBuf<double> shift_tv; // per tree: what the shift needs of (x0, u0) only (hmpc_shift_tree_kernel)
+    DevBuf<double> cert_mats; // the problem's UNSCALED matrices in one block, in the order of hmpc_problem (hmpc_certify_batch)
+    CertProb cert{};          //   sizes, offsets of the rows and views into that block
+    int cert_form = 0, cert_waves = 4, cert_per_cu = 4, cert_cus = 256; // form of hmpc_certify_kernel, chosen at hmpc_create (hmpc_certify_setup)
+    size_t cert_lds = 0;
     DevBuf<double> trace;
     size_t lds = 0;
     int max_grid = 0, last_grid = 0;
@@ -669,6 +674,21 @@ int setup_device(hmpc_handle *h, const HostProblem &hp, const hmpc_problem &q, i
     up(vec(q.Q, (size_t)q.nq * nx), p.Q); up(vec(q.R, (size_t)q.nr * nu), p.R); up(vec(q.Q_T, (size_t)q.nqT * nx), p.QT);
     up(hp.ei, p.ei); up(hp.ej, p.ej);
     if (up.rc) return up.rc;
+    {   // the problem as the caller stated it, for the certificates: with this copy hmpc_certify_batch_device allocates nothing
+        CertProb &c = h->cert;
+        cert_set_sizes(c, q.nx, q.nu, q.nub, q.T, q.nc, q.ncT, q.nq, q.nr, q.nqT);
+        std::vector<double> m;
+        auto add = [&m](const double *a, size_t n) { m.insert(m.end(), a, a + n); };
+        add(q.A, (size_t)nx * nx); add(q.B, (size_t)nx * nu);
+        add(q.F, (size_t)q.nc * nx); add(q.G, (size_t)q.nc * nu); add(q.h, (size_t)q.nc);
+        add(q.F_Tm1, (size_t)q.ncT * nx); add(q.G_Tm1, (size_t)q.ncT * nu); add(q.h_Tm1, (size_t)q.ncT);
+        add(q.Q, (size_t)q.nq * nx); add(q.R, (size_t)q.nr * nu); add(q.Q_T, (size_t)q.nqT * nx);
+        if (m.size() != cert_matrix_doubles(c) || c.n_dual != p.n_dual || c.n_primal != p.n_primal)
+            return fail(HMPC_EINVAL, "the certificate's layout disagrees with the solver's");
+        if (h->cert_mats.alloc(m.size()) != hipSuccess) return fail(HMPC_EDEVICE, "cannot allocate the certificate's matrices");
+        HIPCHK(hipMemcpy(h->cert_mats, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice));
+        cert_set_matrices(c, h->cert_mats);
+    }
 
     const char *per_cu_env = getenv("HMPC_BLOCKS_PER_CU");
     auto fits = [&](size_t lds) { return lds <= LDS_PER_CU && (lds_max <= 0 || lds <= (size_t)lds_max); };
@@ -752,6 +772,8 @@ int setup_device(hmpc_handle *h, const HostProblem &hp, const hmpc_problem &q, i
 
 } // namespace
 
+static int hmpc_certify_setup(hmpc_handle *h, int cus);
+
 extern "C" int hmpc_create(const hmpc_problem *q, const hmpc_options *opt, hmpc_handle **out)
 {
     hmpc_install_backtrace();
@@ -772,6 +794,7 @@ extern "C" int hmpc_create(const hmpc_problem *q, const hmpc_options *opt, hmpc_
     (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
     if ((rc = choose_kernels(h->dp, lds_max, h->cfg, h->jit_libs, h->jit_kernels, nullptr))) return rc;
     if ((rc = setup_device(h.get(), hp, *q, cus, lds_max))) return rc;
+    if ((rc = hmpc_certify_setup(h.get(), cus))) return rc;
     *out = h.release();
     return HMPC_OK;
 }
@@ -1386,6 +1409,126 @@ extern "C" int hmpc_solve_batch(hmpc_handle *h, const double *x0, int32_t x0_str
     }
     return HMPC_OK;
 }
+
+// ---- Certificates of a batch of records (include/hmpc.h; kernel: hmpc_certify.hip, arithmetic: hmpc_certify.h) ----------------
+static int certify_arguments(const void *x0, int32_t x0_stride, int32_t B, const hmpc_result *r, const double *residuals)
+{
+    if (!x0 || !r || !residuals || !r->obj || !r->dual_obj || !r->status || !r->iters || !r->primal || !r->dual)
+        return fail(HMPC_EINVAL, "null argument (all six members of the records are required)");
+    if (x0_stride < 0) return fail(HMPC_EINVAL, "bad x0 stride");
+    return HMPC_OK;
+}
+
+// The form of the kernel for this problem, chosen ONCE at hmpc_create (the launch itself then queries nothing and sets nothing):
+// 2 = rows in LDS where at least four waves' rows fit beside the matrices (one workgroup per CU), 1 = rows in place, matrices in
+// LDS up to 64 KB, 0 = everything in place.  A form whose LDS this device does not grant gives way to the next one HERE, and
+// form 0 needs no grant: a launch never changes form.  The limit on dynamic LDS belongs to the kernel FUNCTION, which every
+// handle of the process shares, so it is set to the most any handle can ask for (form 2: all 160 KB of a CU, form 1: 64 KB of
+// matrices) and never to this handle's own need: a later hmpc_create of a smaller problem leaves an earlier handle's launch its
+// grant.  HMPC_CERTIFY_STAGE = 0 / 1 is a TEST switch, read at hmpc_create only: it caps the form, so that the suite runs all
+// three on problems that would take one.
+static int hmpc_certify_setup(hmpc_handle *h, int cus)
+{
+    const CertProb &c = h->cert;
+    const char *env = getenv("HMPC_CERTIFY_STAGE");
+    const int cap = env ? atoi(env) : 2;
+    const size_t room = 160 * 1024, mats_most = 64 * 1024, mats = cert_matrix_doubles(c) * sizeof(double), per = hmpc_certify_row_doubles(c) * sizeof(double);
+    h->cert_cus = cus > 0 ? cus : 256;
+    h->cert_form = 0; h->cert_waves = CERT_WAVES; h->cert_lds = 0; h->cert_per_cu = 4;
+    if (cap < 1 || mats > mats_most) return HMPC_OK;
+    int waves = cap >= 2 ? (int)((room - mats) / per) : 0;
+    if (waves > CERT_MAX_WAVES) waves = CERT_MAX_WAVES;
+    if (waves >= 4) {
+        const size_t lds = mats + (size_t)waves * per;
+        if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) == hipSuccess) {
+            h->cert_form = 2; h->cert_waves = waves; h->cert_lds = lds; h->cert_per_cu = 1;
+            return HMPC_OK;
+        }
+        (void)hipGetLastError();
+    }
+    if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mats_most) == hipSuccess) {
+        int per_cu = (int)(room / (mats ? mats : 1));
+        h->cert_form = 1; h->cert_lds = mats; h->cert_per_cu = per_cu > 4 ? 4 : per_cu;
+        return HMPC_OK;
+    }
+    (void)hipGetLastError();
+    return HMPC_OK;
+}
+
+static int hmpc_launch_certify(hmpc_handle *h, const CertArgs &a, void *stream)
+{
+    const CertProb &c = h->cert;
+    const hipStream_t st = (hipStream_t)stream;
+    const int waves = h->cert_waves, need = (a.B + waves - 1) / waves, most = h->cert_cus * h->cert_per_cu;
+    const dim3 grid(need < most ? need : most), block(64 * waves);
+    if (h->cert_form == 2) hipLaunchKernelGGL((hmpc_certify_kernel<true, true>), grid, block, h->cert_lds, st, c, a);
+    else if (h->cert_form == 1) hipLaunchKernelGGL((hmpc_certify_kernel<true, false>), grid, block, h->cert_lds, st, c, a);
+    else hipLaunchKernelGGL((hmpc_certify_kernel<false, false>), grid, block, 0, st, c, a);
+    HIPCHK(hipGetLastError());
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_certify_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_stride, const int8_t *d_fix, int32_t B,
+                                         const hmpc_result *d_records, const hmpc_cert_tol *tol, double *d_residuals,
+                                         int32_t *d_verdict, void *stream)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
+    int rc = certify_arguments(d_x0, x0_stride, B, d_records, d_residuals);
+    if (rc) return rc;
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (!d_fix && h->cert.nub > 0) return fail(HMPC_EINVAL, "null argument");
+    if (x0_stride != 0 && x0_stride < h->cert.nx) return fail(HMPC_EINVAL, "bad x0 stride");
+    HIPCHK(hipSetDevice(h->device));
+    const CertArgs a{B, x0_stride, d_x0, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters,
+                     d_records->primal, d_records->dual, tol ? *tol : cert_default_tol(), d_residuals, d_verdict};
+    return hmpc_launch_certify(h, a, stream);
+}
+
+extern "C" int hmpc_certify_batch(hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B,
+                                  const hmpc_result *records, const hmpc_cert_tol *tol, double *residuals, int32_t *verdict)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
+    int rc = certify_arguments(x0, x0_stride, B, records, residuals);
+    if (rc) return rc;
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (!fix && h->cert.nub > 0) return fail(HMPC_EINVAL, "null argument");
+    if (x0_stride != 0 && x0_stride < h->cert.nx) return fail(HMPC_EINVAL, "bad x0 stride");
+    HIPCHK(hipSetDevice(h->device));
+    const CertProb &c = h->cert;
+    // the handle's two staging blocks (as the host-pointer solve uses them): inputs, then the two outputs
+    const size_t n = (size_t)B, nfix = (size_t)c.T * c.nub;
+    struct Part { size_t bytes; const void *src; size_t off; };
+    Part parts[] = {{(x0_stride ? n : 1) * c.nx * sizeof(double), nullptr, 0}, {n * nfix, fix, 0}, {n * sizeof(double), records->obj, 0},
+                    {n * sizeof(double), records->dual_obj, 0}, {n * sizeof(int32_t), records->status, 0}, {n * sizeof(int32_t), records->iters, 0},
+                    {n * c.n_primal * sizeof(double), records->primal, 0}, {n * c.n_dual * sizeof(double), records->dual, 0},
+                    {n * HMPC_CERT_COUNT * sizeof(double), nullptr, 0}, {n * sizeof(int32_t), nullptr, 0}};
+    size_t total = 0;
+    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
+    const size_t in_bytes = parts[8].off;
+    HIPCHK(h->d_stage.grow(total, total, nullptr));
+    HIPCHK(h->h_stage.grow(total, total, nullptr));
+    char *hs = h->h_stage, *ds = h->d_stage;
+    for (size_t b = 0; b < (x0_stride ? n : 1); b++)
+        std::memcpy(hs + b * c.nx * sizeof(double), x0 + b * (size_t)x0_stride, c.nx * sizeof(double));
+    for (const Part &q : parts)
+        if (q.src && q.bytes) std::memcpy(hs + q.off, q.src, q.bytes);
+    HIPCHK(hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, nullptr));
+    const hmpc_result d{(double *)(ds + parts[2].off), (double *)(ds + parts[3].off), (int32_t *)(ds + parts[4].off),
+                        (int32_t *)(ds + parts[5].off), (double *)(ds + parts[6].off), (double *)(ds + parts[7].off)};
+    rc = hmpc_certify_batch_device(h, (const double *)ds, x0_stride ? c.nx : 0, (const int8_t *)(ds + parts[1].off), B, &d, tol,
+                                   (double *)(ds + parts[8].off), (int32_t *)(ds + parts[9].off), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(hs + in_bytes, ds + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    std::memcpy(residuals, hs + parts[8].off, parts[8].bytes);
+    if (verdict) std::memcpy(verdict, hs + parts[9].off, parts[9].bytes);
+    return HMPC_OK;
+}
+
 
 #include "hmpc_fleet.hip" // closed loops in lockstep (same translation unit: uses the launchers above)
 #include "hmpc_comm.hip"  // incumbent all-reduce over RCCL

@@ -48,6 +48,17 @@ class _ShiftMaps(ctypes.Structure):
     _fields_ = [('M_mu', _dp), ('M_rho', _dp), ('V', _dp)]
 
 
+class _CertTol(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_double) for k in ('polished', 'unpolished', 'infeasible', 'weak')]
+
+
+# columns of hmpc_certify_batch's residual matrix (HMPC_CERT_* of include/hmpc.h) and the classes of its verdict's low byte
+CERT_COLUMNS = ('stationarity', 'sign', 'dual_obj', 'primal_equality', 'primal_inequality', 'obj', 'gap',
+                'ray_quadratic', 'ray_objective', 'ray_primal')
+CERT_CLASSES = ('polished', 'unpolished', 'infeasible', 'weak', 'skipped')
+CERT_FAILED = 0x100
+
+
 _lib = None
 
 
@@ -87,6 +98,11 @@ def load_library():
         lib.hmpc_shift_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 13
         lib.hmpc_shift_batch_device.restype = ctypes.c_int
         lib.hmpc_shift_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 14
+        lib.hmpc_certify_batch.restype = ctypes.c_int
+        lib.hmpc_certify_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                           ctypes.POINTER(_Result), ctypes.POINTER(_CertTol), ctypes.c_void_p, ctypes.c_void_p]
+        lib.hmpc_certify_batch_device.restype = ctypes.c_int
+        lib.hmpc_certify_batch_device.argtypes = lib.hmpc_certify_batch.argtypes + [ctypes.c_void_p]
         lib.hmpc_fleet_create.restype = ctypes.c_int
         lib.hmpc_fleet_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
         lib.hmpc_fleet_destroy.restype = ctypes.c_int
@@ -132,7 +148,7 @@ def load_library():
 
 EXPORTED_SYMBOLS = ('hmpc_create', 'hmpc_destroy', 'hmpc_record_sizes', 'hmpc_launch_info', 'hmpc_kernel_info', 'hmpc_kernel_recipe', 'hmpc_jit_stats', 'hmpc_jit_build_problem', 'hmpc_validate_kernels', 'hmpc_second_opinion_review',
                     'hmpc_solve_batch', 'hmpc_solve_batch_device', 'hmpc_last_error',
-                    'hmpc_set_shift_maps', 'hmpc_shift_batch', 'hmpc_shift_batch_device',
+                    'hmpc_set_shift_maps', 'hmpc_shift_batch', 'hmpc_shift_batch_device', 'hmpc_certify_batch', 'hmpc_certify_batch_device',
                     'hmpc_fleet_create', 'hmpc_fleet_destroy', 'hmpc_fleet_reset', 'hmpc_fleet_stop', 'hmpc_fleet_rows', 'hmpc_fleet_solve', 'hmpc_fleet_shift',
                     'hmpc_fleet_stats', 'hmpc_fleet_uncertified', 'hmpc_fleet_handdown', 'hmpc_fleet_timing', 'hmpc_comm_unique_id', 'hmpc_comm_create', 'hmpc_allreduce_incumbent', 'hmpc_allreduce_incumbent_device', 'hmpc_publish_incumbent', 'hmpc_comm_destroy',
                     'hmpc_lp_solve_batch')
@@ -432,3 +448,77 @@ class HipBatchedQP(object):
                                                      fix.data_ptr(), lb.data_ptr(), dual.data_ptr(), dual_obj.data_ptr(),
                                                      out['fix'].data_ptr(), out['lb'].data_ptr(), out['dual'].data_ptr(),
                                                      out['dual_obj'].data_ptr(), out['flags'].data_ptr(), ctypes.c_void_p(stream)))
+
+    # ------------------------------------------------------------------
+    # certificates of a batch of records (KKT point / Farkas ray) on the device
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _cert_tol(tol):
+        if tol is None:
+            return None
+        return ctypes.byref(_CertTol(*[float(tol[k]) for k in ('polished', 'unpolished', 'infeasible', 'weak')]))
+
+    def certify_batch(self, x0, fix, rec, tol=None):
+        """Every record of ``rec`` (a dict as ``solve_batch`` returns it, all of obj, dual_obj, status, iters, primal, dual) held
+        to its own certificate on the device (``hmpc_certify_batch``; host arrays in and out).
+
+        x0, fix : as for ``solve_batch``;  tol : optional dict polished / unpolished / infeasible / weak (default 1e-8, 5e-6,
+        1e-6, 1e-6).  Returns ``{name: float64 [B]}`` under the names of ``CERT_COLUMNS`` (NaN where a residual does not
+        apply to the record's status), ``'class'`` (one of ``CERT_CLASSES`` per record), ``'failed'`` (bool) and
+        ``'failed_mask'`` (bit c: column c of ``CERT_COLUMNS`` lies over its tolerance, or is NaN).
+        """
+        fix = np.ascontiguousarray(fix, dtype=np.int8)
+        if fix.ndim != 2 or fix.shape[1] != self.nfix:
+            raise ValueError('fix must have shape (B, %d).' % self.nfix)
+        B = fix.shape[0]
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape == (self.nx,):
+            stride = 0
+        elif x0.shape == (B, self.nx):
+            stride = self.nx
+        else:
+            raise ValueError('x0 must have shape (%d,) or (%d, %d).' % (self.nx, B, self.nx))
+        # the iters word of the C ABI: solve_batch splits its flags off (a handed-down record of the oracle carries polished = 64)
+        iters = np.asarray(rec['iters']).astype(np.int64) & 0xFFFF
+        if rec.get('polished') is not None:
+            iters |= np.where(np.asarray(rec['polished']) > 0, 0x10000, 0)
+        if rec.get('weak') is not None:
+            iters |= np.where(np.asarray(rec['weak']) > 0, 0x20000, 0)
+        keep = dict(obj=np.ascontiguousarray(rec['obj'], dtype=np.float64), dual_obj=np.ascontiguousarray(rec['dual_obj'], dtype=np.float64),
+                    status=np.ascontiguousarray(rec['status'], dtype=np.int32), iters=np.ascontiguousarray(iters, dtype=np.int32),
+                    primal=np.ascontiguousarray(rec['primal'], dtype=np.float64), dual=np.ascontiguousarray(rec['dual'], dtype=np.float64))
+        if keep['primal'].shape != (B, self.n_primal) or keep['dual'].shape != (B, self.n_dual) or \
+                any(keep[k].shape != (B,) for k in ('obj', 'dual_obj', 'status', 'iters')):
+            raise ValueError('record arrays have inconsistent shapes.')
+        res = np.empty((B, len(CERT_COLUMNS)))
+        verdict = np.empty(B, dtype=np.int32)
+        r = _Result(**{k: v.ctypes.data for k, v in keep.items()})
+        self._check(self.lib.hmpc_certify_batch(self.handle, x0.ctypes.data, stride, fix.ctypes.data, B, ctypes.byref(r),
+                                                self._cert_tol(tol), res.ctypes.data, verdict.ctypes.data))
+        out = {name: res[:, c].copy() for c, name in enumerate(CERT_COLUMNS)}
+        out['class'] = np.array(CERT_CLASSES, dtype=object)[verdict & 0xFF]
+        out['failed'] = (verdict & CERT_FAILED) != 0
+        out['failed_mask'] = (verdict >> 16) & 0xFFFF
+        return out
+
+    def certify_batch_device(self, x0, fix, out, residuals, verdict, stream=None, tol=None):
+        """Device-resident form: torch CUDA tensors, asynchronous on ``stream`` (default: torch's current stream).  ``out`` is
+        exactly the dict ``solve_batch_device`` filled (all six tensors), so a solve followed by this call on one stream
+        certifies a frontier without a host round trip.  residuals : float64 [B, 10] (columns: ``CERT_COLUMNS``);
+        verdict : int32 [B] or None (low byte: index into ``CERT_CLASSES``, ``CERT_FAILED``, failing columns from bit 16)."""
+        import torch
+        B = fix.shape[0]
+        assert fix.dtype == torch.int8 and fix.is_cuda and fix.is_contiguous() and fix.shape[1] == self.nfix
+        assert x0.dtype == torch.float64 and x0.is_cuda and x0.is_contiguous()
+        stride = 0 if x0.dim() == 1 else self.nx
+        for k, dtype in (('obj', torch.float64), ('dual_obj', torch.float64), ('status', torch.int32), ('iters', torch.int32),
+                         ('primal', torch.float64), ('dual', torch.float64)):
+            assert out[k].is_cuda and out[k].is_contiguous() and out[k].dtype == dtype and out[k].shape[0] == B, k
+        assert residuals.is_cuda and residuals.is_contiguous() and residuals.dtype == torch.float64 and residuals.shape == (B, len(CERT_COLUMNS))
+        assert verdict is None or (verdict.is_cuda and verdict.is_contiguous() and verdict.dtype == torch.int32 and verdict.shape == (B,))
+        res = _Result(**{k: out[k].data_ptr() for k in ('obj', 'dual_obj', 'status', 'iters', 'primal', 'dual')})
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        self._check(self.lib.hmpc_certify_batch_device(self.handle, x0.data_ptr(), stride, fix.data_ptr() if self.nfix else None, B,
+                                                       ctypes.byref(res), self._cert_tol(tol), residuals.data_ptr(),
+                                                       verdict.data_ptr() if verdict is not None else None, ctypes.c_void_p(stream)))
