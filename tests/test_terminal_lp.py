@@ -6,6 +6,7 @@ Three solvers of the same batched call ``lp(A, c, b, relax) -> obj, x, z, status
     committed fixtures and the LP forms of the reference's known answers (test_bounded_qp.py:145-205,
     test_controller.py:40-59);
   * the HIP kernel through the C ABI (``hmpc_lp_solve_batch``) -- ``-m gpu``, same assertions plus parity with the oracle.
+Every exit of the kernel, a workgroup's later LPs and the records' certificates to rounding: tests/test_lp_certificates.py.
 """
 import numpy as np
 import pytest
