@@ -110,8 +110,9 @@ typedef struct hmpc_result {
                       /*     bit 16 (HMPC_ITERS_POLISHED): the record is the polished vertex    */
                       /*     solution (exactly complementary), not the interior-point iterate.  */
                       /*     An OPTIMAL record WITHOUT the bit is the iterate that met the      */
-                      /*     stopping test (gap <= 1e-8, or 1e-6 at the floor of the barrier    */
-                      /*     parameter): optimal to that tolerance and carrying its own KKT     */
+                      /*     stopping test (gap <= tol = 1e-8, or 100 tol = 1e-6 at the floor   */
+                      /*     of the barrier parameter; ON THE SCALED COST, see below): optimal  */
+                      /*     to that tolerance and carrying its own KKT                         */
                       /*     certificate, but reproducible across arithmetic orders only to     */
                       /*     ~1e-4 in the trajectory.  Every optimal node of the cart-pole      */
                       /*     systems polishes; 2 % of BASELINE configs[4]'s do not;              */
@@ -123,6 +124,21 @@ typedef struct hmpc_result {
     double *primal;   /* B x n_primal                                                         */
     double *dual;     /* B x n_dual                                                           */
 } hmpc_result;
+/* What a record owes the options it was solved with (tests/test_solver_options.py).
+ *   Units of the stopping test.  The solver works on the cost scaled by 1 / H, H the largest entry of the cost's Hessian
+ *     2 (Q'Q (+) R'R), 2 Q_T'Q_T, and tests  |p - d| <= tol (1 + min(|p|, |d|))  THERE.  In the caller's units the relative gap
+ *     |obj - dual_obj| / (1 + |obj|) of an unpolished OPTIMAL record is therefore at most  tol max(1, H)  where the iterate met
+ *     tol, and at most  100 tol max(1, H)  where it left at the floor of the barrier parameter (mu < 1e-11, residuals and gap within
+ *     100 tol: the iteration has nothing more to give).  That exit has been measured only without refinement (refine = 0: the
+ *     dual residual then grows as mu falls and the iterate never meets tol; 2.5e-5 on the cart-pole with walls, H = 36.4) and
+ *     with tol = 1e-10, which an unpolished record does not follow below about 1e-7 / H.  A POLISHED record is a verified vertex
+ *     and does not depend on tol.
+ *   max_iter caps every solve of a node: iters & 0xFFFF <= max_iter, or 2 max_iter where the terminal set is tried lazily
+ *     (lazy_terminal = 1 and ncT > nc: up to two solves).  A capped solve is the uncapped one cut off.
+ *   A record of status >= HMPC_MAXITER carries none of HMPC_ITERS_POLISHED, _WEAK, _UNCERTIFIED, _HANDED (each is raised on the
+ *     exit that decides a node); its rows and objectives are the last iterate's and promise nothing.
+ *   polish = 0: nothing is handed down either (hmpc_warm is ignored: the cold records bit for bit, but for HMPC_ITERS_TERMINAL).
+ *   tol, tol_inf, max_iter, polish_tol <= 0 are the defaults; lazy_terminal, refine, polish are taken as they stand. */
 
 /* Parent -> child hand-down (nullable everywhere).  The reference hands the parent node's simplex basis to the child
  * (controller.py:260-264, 426; subproblem_solution.py:37-43, with Gurobi's dual simplex); here the child receives the

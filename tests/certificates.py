@@ -110,11 +110,18 @@ def worst_per_class(res, kind):
     return worst
 
 
-def assert_certified(ctrl, x0, fix, rec, ref=None, what='', margins=None):
+def _base_of(base, cls, name):
+    """base[cls]: one number for every residual of the class, or {residual: number, None: every other residual}."""
+    b = base[cls]
+    return b.get(name, b[None]) if isinstance(b, dict) else b
+
+
+def assert_certified(ctrl, x0, fix, rec, ref=None, what='', margins=None, base=BASE, ref_classes=CLASSES):
     """Every record of ``rec`` certifies itself, class by class and residual by residual, to BASE[class] -- or, where ``ref``
     (the oracle's records of the SAME workload) is given, to max(BASE[class], REF_FACTOR x the reference's worst value of that
     residual in that class).  Returns the number of records per class and of skipped ones (status > 1).  ``margins``
-    (new_margins()) takes in what was measured, once everything has passed."""
+    (new_margins()) takes in what was measured, once everything has passed.  ``base``: other class bases than BASE -- those of
+    records solved at other options than the defaults (option_checks.bases_at) --, ``ref_classes``: the classes ``ref`` may widen."""
     res, kind = residuals(ctrl, x0, fix, rec), classify(rec)
     assert np.array_equal(kind == 'skipped', res['skipped'])           # no record of status <= 1 is left out
     worst = worst_per_class(res, kind)
@@ -124,7 +131,7 @@ def assert_certified(ctrl, x0, fix, rec, ref=None, what='', margins=None):
     for cls, values in worst.items():
         for name, value in values.items():
             reference = ref_worst.get(cls, {}).get(name, 0.)
-            bound = 0. if name in EXACT else max(BASE[cls], REF_FACTOR * reference if np.isfinite(reference) else 0.)
+            bound = 0. if name in EXACT else max(_base_of(base, cls, name), REF_FACTOR * reference if np.isfinite(reference) and cls in ref_classes else 0.)
             if not value <= bound:
                 rows = np.flatnonzero(kind == cls)
                 at = int(rows[np.argmax(np.where(np.isnan(res[name][rows]), np.inf, res[name][rows]))])

@@ -229,6 +229,13 @@ class HipBatchedQP(object):
     problem : dict as returned by ``HybridModelPredictiveController.problem_data()``
     tol, tol_inf, max_iter, lazy_terminal, refine, polish, polish_tol : see ``hmpc_options`` in include/hmpc.h
     device : HIP device ordinal (-1: current device)
+
+    What a record owes these options (tests/test_solver_options.py): ``max_iter`` caps every pass of a
+    node (two where the terminal set is tried lazily); a node left undecided (status >= 2) carries none of the flags ``polished``,
+    ``weak``, ``uncertified``, ``handed``, and its rows and objectives are the last iterate's: they promise nothing.  An OPTIMAL record
+    without ``polished`` met the stopping test on the SCALED cost: its relative gap is at most ``100 tol max(1, H)`` in the caller's
+    units, H the largest entry of the cost's Hessian -- at the floor of the barrier parameter, an exit measured only without
+    refinement (``refine=False``) and at ``tol=1e-10`` (include/hmpc.h, below ``hmpc_result``).  With ``polish=False`` nothing is handed down (``warm`` returns the cold records).
     """
 
     def __init__(self, problem, tol=1e-8, tol_inf=1e-6, max_iter=100, lazy_terminal=True, refine=True, device=-1,
