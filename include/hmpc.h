@@ -272,6 +272,66 @@ int hmpc_certify_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_str
                               const hmpc_result *d_records, const hmpc_cert_tol *tol /* nullable, host */,
                               double *d_residuals, int32_t *d_verdict /* nullable */, void *stream);
 
+/* ---- Branching a batch of solved nodes (records -> children with their lower bounds) --------------------------
+ * The step of a branch-and-bound round between two solves: the reference's brancher (warm_start_hmpc/controller.py:395-429
+ * _brancher: a child's bound is its parent's objective plus the parent's multiplier of the bound the branch tightens) with its
+ * branching rule (controller.py:13-44 branch_in_time) and the prune / incumbent / branch decision of
+ * branch_and_bound.py:476-489, for B records at once on the device (csrc/hmpc_branch.hip; per-node arithmetic:
+ * csrc/hmpc_branch.h).  Per node b, from its row of `fix`, its record and cutoff[b] (cutoff NULL: +inf):
+ *   pos        1 + the largest j with fix[j] >= 0, 0 if there is none: the binary branch_in_time fixes next, for ANY
+ *              identifier, not only chronological prefixes; pos == T*nub: every binary is fixed
+ *   child_lb2  [0] = obj + nu_ub[pos] (the 0-branch), [1] = obj + nu_lb[pos] (the 1-branch): one float64 addition each;
+ *              both +inf when pos == T*nub or the node is not OPTIMAL
+ *   word       exactly one of HMPC_BRANCH_BRANCHED / _COMPLETE / _PRUNED / _INFEASIBLE / _FAILED, and the flags below.
+ *              obj is compared as `obj < cutoff`: a NaN objective (or cutoff) compares false and ends as PRUNED, never
+ *              as BRANCHED or COMPLETE
+ *   bits       ceil(T*nub / 64) words: bit j = the relaxed binary j of the primal row > 0.5 (NaN: 0) -- the rounding the
+ *              fleet's dive prediction uses; only for a VERTEX node with pos < T*nub, zero otherwise
+ * Children: the nodes flagged BRANCHED have two each, 0-branch first, in the order of the batch -- child_offset[b] is the
+ * exclusive prefix sum of (2 if BRANCHED else 0), n_children[0] its total; rows child_offset[b] + v of
+ *   child_fix     the parent's identifier with fix[pos] = v
+ *   child_lb      child_lb2[v]
+ *   child_parent  b
+ *   child_warm    warm_base + b if the parent is a VERTEX (its record may be handed down: ready to be hmpc_warm.index of
+ *                 the next solve, whose rows are the records of this batch from row warm_base on), else -1
+ * Rows of the child arrays at and beyond n_children are not written.  mark_weak != 0: records->dual_obj[b] of a node with
+ * HMPC_ITERS_WEAK becomes -inf (the node prunes at this step only: the warm-start shift then reopens the leaf whatever the
+ * model error, controller.py:555-558); no other entry of the records is written.
+ * records: obj, status, iters required; dual where child_lb2 or child_lb is asked for, primal where bits is, dual_obj
+ * where mark_weak is set.  A problem without binaries has nothing to branch on: HMPC_EINVAL.  B == 0: HMPC_OK, nothing touched. */
+#define HMPC_BRANCH_BRANCHED    0x01  /* OPTIMAL, obj < cutoff, pos < T*nub: two children */
+#define HMPC_BRANCH_COMPLETE    0x02  /* OPTIMAL, obj < cutoff, pos == T*nub: an incumbent candidate */
+#define HMPC_BRANCH_PRUNED      0x04  /* OPTIMAL, not (obj < cutoff) */
+#define HMPC_BRANCH_INFEASIBLE  0x08  /* status HMPC_INFEASIBLE */
+#define HMPC_BRANCH_FAILED      0x10  /* status > HMPC_INFEASIBLE: the record must not be used */
+#define HMPC_BRANCH_VERTEX      0x100 /* OPTIMAL and HMPC_ITERS_POLISHED: the record may be handed down */
+#define HMPC_BRANCH_WEAK        0x200 /* HMPC_ITERS_WEAK */
+#define HMPC_BRANCH_UNCERTIFIED 0x400 /* HMPC_ITERS_UNCERTIFIED */
+#define HMPC_BRANCH_HANDED      0x800 /* HMPC_ITERS_HANDED */
+typedef struct hmpc_branch_out {  /* any member may be NULL (not wanted) */
+    double   *obj;          /* B : copy of records->obj                                     */
+    int32_t  *word, *pos;   /* B, B                                                         */
+    double   *child_lb2;    /* B x 2                                                        */
+    uint64_t *bits;         /* B x ceil(T*nub/64)                                           */
+    int32_t  *child_offset; /* B : required if any child_* is set                           */
+    int32_t  *n_children;   /* 1                                                            */
+    int8_t   *child_fix;    /* 2B x T*nub                                                   */
+    double   *child_lb;     /* 2B                                                           */
+    int32_t  *child_parent; /* 2B                                                           */
+    int32_t  *child_warm;   /* 2B                                                           */
+} hmpc_branch_out;
+/* Host-pointer form: copies in, runs, copies out (the child arrays up to n_children; records->dual_obj when mark_weak is
+ * set), returns when done.  Replaces B calls of controller.py:395-429. */
+int hmpc_branch_batch(hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *records, const double *cutoff /* nullable */,
+                      int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *out);
+/* Device-pointer form: every pointer (and every member of d_records and d_out) is device memory; asynchronous on `stream`.
+ * Up to three launches (digest, offsets, children), no allocation, no synchronisation, no workspace of the handle: it is
+ * legal between two hmpc_solve_batch_device calls on one stream, so that solve -> branch -> solve (controller.py:395-429
+ * between two passes of branch_and_bound.py:462-489) runs without a row leaving HBM -- the caller reads back n_children
+ * alone, to size the next launch. */
+int hmpc_branch_batch_device(hmpc_handle *h, const int8_t *d_fix, int32_t B, const hmpc_result *d_records, const double *d_cutoff /* nullable */,
+                             int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *d_out, void *stream);
+
 /* ---- Closed loops in lockstep ("fleet") ---------------------------------------------------------------
  * K independent closed loops of the controller advanced together -- the shape of the reference's Monte-Carlo
  * study (notebooks/cart_pole_with_walls/statistical_analysis.py:93-196: per step one warm-started branch and
@@ -315,6 +375,14 @@ int hmpc_fleet_uncertified(const hmpc_fleet *f, int64_t *pruned, int64_t *search
  * round than its parent receives the parent's record, which already lies in the fleet's HBM pools.  enable: 1 / 0, < 0:
  * leave as is.  verified (nullable): solves since creation whose handed-down active set verified. */
 int hmpc_fleet_handdown(hmpc_fleet *f, int32_t enable, int64_t *verified);
+/* Digest of a round on the device (off by default): the digest kernel of the branching entries above runs behind the QP
+ * kernel on the fleet's stream, and a round copies back ONE block of objective, word, pos, the two child bounds and -- with
+ * dive prediction -- the rounded binaries per node (32 + 8 ceil(T nub / 64) bytes) in place of objective, status, iters, a
+ * strided row of 2 T nub multipliers and, with dive prediction, the whole primal row; the dual objective of a weak node is
+ * set to -inf by the kernel and not by one blocking copy per node.  The tree stays on the host: selection, consumption order
+ * and every result are those of the default path, bit for bit (controller.py:395-429 on the device, branch_and_bound.py:
+ * 476-489 on the host).  enable: 1 / 0, < 0: leave as is. */
+int hmpc_fleet_digest(hmpc_fleet *f, int32_t enable);
 /* Host wall time of the fleet's calls by phase since creation (5 doubles, seconds): candidate selection, staging of the
  * rounds' nodes, device (copies, kernel, synchronisation), consumption of the results, node shifts. */
 int hmpc_fleet_timing(const hmpc_fleet *f, double *seconds5);

@@ -22,6 +22,7 @@
 #include "hmpc_jit.h"      // register kernels for shapes without a built-in instantiation, compiled at hmpc_create
 #include "hmpc_shift.hip"
 #include "hmpc_certify.hip" // certificates of a batch of records (hmpc_certify_batch)
+#include "hmpc_branch.hip"  // branching a batch of solved nodes (hmpc_branch_batch)
 
 #define HMPC_CHECK_NODES 64 // (even) nodes of the first-use check of a kernel compiled at hmpc_create (hmpc_check_compiled)
 static thread_local std::string g_err;
@@ -1529,6 +1530,127 @@ extern "C" int hmpc_certify_batch(hmpc_handle *h, const double *x0, int32_t x0_s
     return HMPC_OK;
 }
 
+// ---- Branching a batch of solved nodes (include/hmpc.h; kernels: hmpc_branch.hip, arithmetic: hmpc_branch.h) -------------------
+static BranchDims branch_dims_of(const hmpc_handle *h)
+{
+    const CertProb &c = h->cert; // (the sizes as the caller of hmpc_create stated them)
+    return branch_dims(c.nx, c.nu, c.nub, c.T, c.nc, c.ncL, c.nq, c.nr, c.nqT);
+}
+
+// everything that can be said about the arguments without the device
+static int branch_arguments(const hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *r, int32_t mark_weak, const hmpc_branch_out *out)
+{
+    if (!fix || !r || !out) return fail(HMPC_EINVAL, "branch: null argument (fix, records and out are required)");
+    if (!r->obj || !r->status || !r->iters) return fail(HMPC_EINVAL, "branch: null argument (obj, status and iters of the records are required)");
+    if ((out->child_lb2 || out->child_lb) && !r->dual) return fail(HMPC_EINVAL, "branch: the child bounds need the records' dual rows");
+    if (out->bits && !r->primal) return fail(HMPC_EINVAL, "branch: the rounded bits need the records' primal rows");
+    if (mark_weak && !r->dual_obj) return fail(HMPC_EINVAL, "branch: mark_weak needs the records' dual objectives");
+    if ((out->child_fix || out->child_lb || out->child_parent || out->child_warm) && !out->child_offset)
+        return fail(HMPC_EINVAL, "branch: the child arrays need child_offset");
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (h->cert.nub <= 0) return fail(HMPC_EINVAL, "branch: the problem has no binaries (nub == 0)");
+    if (B > (1 << 30)) return fail(HMPC_EINVAL, "branch: bad batch size (the children of more than 2^30 nodes have no int32 offsets)");
+    return HMPC_OK;
+}
+
+// digest, then -- where asked for -- offsets and children, back to back on `stream`: no allocation, no synchronisation
+static int hmpc_launch_branch(const BranchDims &d, const BranchArgs &a, hipStream_t st)
+{
+    const int need = (a.B + BRANCH_WAVES - 1) / BRANCH_WAVES;
+    const dim3 grid(need < BRANCH_MAX_GRID ? need : BRANCH_MAX_GRID), block(64 * BRANCH_WAVES);
+    const hmpc_branch_out &o = a.out;
+    if (o.obj || o.word || o.pos || o.child_lb2 || o.bits || o.child_offset || a.mark_weak) {
+        hipLaunchKernelGGL(hmpc_branch_digest_kernel, grid, block, 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (o.child_offset || o.n_children) {
+        hipLaunchKernelGGL(hmpc_branch_offsets_kernel, dim3(1), dim3(BRANCH_SCAN_CHUNK), 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (o.child_fix || o.child_lb || o.child_parent || o.child_warm) {
+        hipLaunchKernelGGL(hmpc_branch_children_kernel, grid, block, 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_branch_batch_device(hmpc_handle *h, const int8_t *d_fix, int32_t B, const hmpc_result *d_records, const double *d_cutoff,
+                                        int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *d_out, void *stream)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of, and nothing is touched: n_children neither)
+    int rc = branch_arguments(h, d_fix, B, d_records, mark_weak, d_out);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const BranchArgs a{B, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters, d_records->primal, d_records->dual,
+                       d_cutoff, warm_base, mark_weak != 0, *d_out};
+    return hmpc_launch_branch(branch_dims_of(h), a, (hipStream_t)stream);
+}
+
+extern "C" int hmpc_branch_batch(hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *records, const double *cutoff,
+                                 int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *out)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK;
+    int rc = branch_arguments(h, fix, B, records, mark_weak, out);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const BranchDims d = branch_dims_of(h);
+    const size_t n = (size_t)B, nfix = (size_t)d.nfix;
+    const bool children = out->child_fix || out->child_lb || out->child_parent || out->child_warm;
+    // the handle's two staging blocks (as the host-pointer solve uses them): inputs, then outputs; a part nobody asks for has no bytes
+    enum { P_FIX, P_OBJ, P_STATUS, P_ITERS, P_PRIMAL, P_DUAL, P_CUTOFF, P_DOBJ, O_OBJ, O_WORD, O_POS, O_LB2, O_BITS, O_OFF, O_N, O_CFIX, O_CLB, O_CPAR, O_CWARM, PARTS };
+    struct Part { size_t bytes; const void *src; void *dst; size_t off; };
+    Part parts[PARTS] = {{n * nfix, fix, nullptr, 0},
+                         {n * sizeof(double), records->obj, nullptr, 0},
+                         {n * sizeof(int32_t), records->status, nullptr, 0},
+                         {n * sizeof(int32_t), records->iters, nullptr, 0},
+                         {out->bits ? n * d.n_primal * sizeof(double) : 0, records->primal, nullptr, 0},
+                         {(out->child_lb2 || out->child_lb) ? n * d.n_dual * sizeof(double) : 0, records->dual, nullptr, 0},
+                         {cutoff ? n * sizeof(double) : 0, cutoff, nullptr, 0},
+                         {mark_weak ? n * sizeof(double) : 0, records->dual_obj, records->dual_obj, 0}, // (in and out: first of the outputs)
+                         {out->obj ? n * sizeof(double) : 0, nullptr, out->obj, 0},
+                         {out->word ? n * sizeof(int32_t) : 0, nullptr, out->word, 0},
+                         {out->pos ? n * sizeof(int32_t) : 0, nullptr, out->pos, 0},
+                         {out->child_lb2 ? 2 * n * sizeof(double) : 0, nullptr, out->child_lb2, 0},
+                         {out->bits ? n * d.words * sizeof(uint64_t) : 0, nullptr, out->bits, 0},
+                         {out->child_offset ? n * sizeof(int32_t) : 0, nullptr, out->child_offset, 0},
+                         {(out->n_children || children) ? sizeof(int32_t) : 0, nullptr, out->n_children, 0}, // (the children are copied out up to it)
+                         {out->child_fix ? 2 * n * nfix : 0, nullptr, out->child_fix, 0},
+                         {out->child_lb ? 2 * n * sizeof(double) : 0, nullptr, out->child_lb, 0},
+                         {out->child_parent ? 2 * n * sizeof(int32_t) : 0, nullptr, out->child_parent, 0},
+                         {out->child_warm ? 2 * n * sizeof(int32_t) : 0, nullptr, out->child_warm, 0}};
+    size_t total = 0;
+    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
+    const size_t out_begin = parts[P_DOBJ].off;
+    HIPCHK(h->d_stage.grow(total, total, nullptr));
+    HIPCHK(h->h_stage.grow(total, total, nullptr));
+    char *hs = h->h_stage, *ds = h->d_stage;
+    for (int i = 0; i <= P_DOBJ; i++)
+        if (parts[i].bytes) std::memcpy(hs + parts[i].off, parts[i].src, parts[i].bytes);
+    HIPCHK(hipMemcpyAsync(ds, hs, parts[O_OBJ].off, hipMemcpyHostToDevice, nullptr));
+    auto dev = [&](int i) -> char * { return parts[i].bytes ? ds + parts[i].off : nullptr; };
+    const hmpc_result r{(double *)dev(P_OBJ), (double *)dev(P_DOBJ), (int32_t *)dev(P_STATUS), (int32_t *)dev(P_ITERS), (double *)dev(P_PRIMAL), (double *)dev(P_DUAL)};
+    const hmpc_branch_out o{(double *)dev(O_OBJ), (int32_t *)dev(O_WORD), (int32_t *)dev(O_POS), (double *)dev(O_LB2), (uint64_t *)dev(O_BITS), (int32_t *)dev(O_OFF),
+                            (int32_t *)dev(O_N), (int8_t *)dev(O_CFIX), (double *)dev(O_CLB), (int32_t *)dev(O_CPAR), (int32_t *)dev(O_CWARM)};
+    rc = hmpc_branch_batch_device(h, (const int8_t *)ds, B, &r, (const double *)dev(P_CUTOFF), warm_base, mark_weak, &o, nullptr);
+    if (rc) return rc;
+    if (total > out_begin) HIPCHK(hipMemcpyAsync(hs + out_begin, ds + out_begin, total - out_begin, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    int32_t nchild = 0;
+    if (parts[O_N].bytes) std::memcpy(&nchild, hs + parts[O_N].off, sizeof nchild);
+    if (nchild < 0 || (size_t)nchild > 2 * n) return fail(HMPC_EDEVICE, "branch: the device returned a number of children outside [0, 2 B]");
+    for (int i = P_DOBJ; i < PARTS; i++) {
+        const Part &q = parts[i];
+        if (!q.bytes || !q.dst) continue;
+        // (rows of the child arrays at and beyond n_children are not written: neither on the device nor here)
+        const size_t bytes = i >= O_CFIX ? q.bytes / (2 * n) * (size_t)nchild : q.bytes;
+        std::memcpy(q.dst, hs + q.off, bytes);
+    }
+    return HMPC_OK;
+}
 
 #include "hmpc_fleet.hip" // closed loops in lockstep (same translation unit: uses the launchers above)
 #include "hmpc_comm.hip"  // incumbent all-reduce over RCCL

@@ -13,7 +13,8 @@
 //     leaves HBM; children reference their parent's row by index; the node shift (hmpc_shift.hip) reads the leaves'
 //     rows through that index and writes the next step's pool.  Per round the host uploads the candidates'
 //     identifiers and initial states (112 B per node) and downloads objective, status and the multipliers of the
-//     binaries' bounds (1.3 KB per node) through pinned staging, on one stream.
+//     binaries' bounds (1.3 KB per node) through pinned staging, on one stream -- or, with hmpc_fleet_digest, the digest
+//     of the round that hmpc_branch.hip computes behind the QP kernel: one block of 48 B per node at T nub = 80.
 // Semantics per tree are those of warm_start_hmpc_amd/batched.py (feedforward_many / construct_warm_start_many),
 // against which tests/test_fleet.py checks it step by step.
 // The host's share of a step is in hmpc_tree.h, free of HIP, where it runs under sanitizers (tests/host/tree_driver.cpp);
@@ -49,6 +50,9 @@ struct hmpc_fleet {
     DevBuf<uint8_t> d_flags;
     PinBuf<uint8_t> h_flags;
     int handdown = 1; // parent -> child hand-down of active sets (hmpc_fleet_options)
+    int digest = 0;   // a round's results come back as the digest of hmpc_branch.hip, one block per round (hmpc_fleet_digest)
+    DevBuf<char> d_digest; // per node: obj, two child bounds, the words of rounded bits, word, pos -- array after array (fleet_digest_layout)
+    PinBuf<char> h_digest;
     DevBuf<double> d_kx0, d_ku0, d_ke0; // K x nx, K x nu, K x nx
     PinBuf<double> h_k;                 //   their pinned mirror (3 blocks)
     PinBuf<double> h_bits;              // dive prediction: primal rows of a round's nodes
@@ -106,6 +110,22 @@ struct Phase {
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 };
 
+// The digest of a round of B nodes as ONE block, so that one copy brings it back: obj (B doubles) | child bounds (2 B doubles)
+// | rounded bits (B x words) | word (B) | pos (B).
+struct FleetDigest { size_t obj, lb2, bits, word, pos, bytes; };
+inline size_t fleet_digest_node_bytes(size_t words) { return 3 * sizeof(double) + words * sizeof(uint64_t) + 2 * sizeof(int32_t); }
+inline FleetDigest fleet_digest_layout(size_t B, size_t words)
+{
+    FleetDigest L;
+    L.obj = 0;
+    L.lb2 = L.obj + B * sizeof(double);
+    L.bits = L.lb2 + 2 * B * sizeof(double);
+    L.word = L.bits + B * words * sizeof(uint64_t);
+    L.pos = L.word + B * sizeof(int32_t);
+    L.bytes = L.pos + B * sizeof(int32_t);
+    return L;
+}
+
 // Room in the round buffers for B nodes: one that is short is replaced by room for max(2B, 1024) nodes.
 int fleet_ensure_round(hmpc_fleet *f, size_t B)
 {
@@ -122,6 +142,10 @@ int fleet_ensure_round(hmpc_fleet *f, size_t B)
     grow(f->d_widx, 1); grow(f->h_widx, 1);
     grow(f->d_lb, 1); grow(f->h_lb, 1); grow(f->d_lb_out, 1);
     grow(f->d_flags, 1); grow(f->h_flags, 1);
+    if (f->digest) { // (sized here with the other round buffers, never between the launches of a round)
+        const size_t per = fleet_digest_node_bytes((nfix + 63) / 64);
+        grow(f->d_digest, per); grow(f->h_digest, per);
+    }
     if (e != hipSuccess) return fail(HMPC_EDEVICE, "fleet: cannot allocate the round buffers");
     return HMPC_OK;
 }
@@ -271,28 +295,51 @@ extern "C" int hmpc_fleet_solve(hmpc_fleet *f, const double *x0, int32_t width, 
             hmpc_warm hw{f->ppool, f->pool[f->cur], f->d_widx, (int32_t)f->used};
             if (any_warm) HIPCHK(hipMemcpyAsync(f->d_widx, f->h_widx, B * sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
             if ((rc = hmpc_solve_batch_device(h, f->d_x0, nx, f->d_fix, (int32_t)B, any_warm ? &hw : nullptr, &r, f->stream))) return rc;
-            HIPCHK(hipMemcpyAsync(f->h_obj, f->d_obj, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipMemcpyAsync(f->h_status, f->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipMemcpyAsync(f->h_iters, f->d_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-            if (ex.dive) { // the round's primal rows: the rounded binaries of its vertex nodes predict their descendants' dives
-                if (f->h_bits.grow(B * d.n_primal, 2 * B * d.n_primal, f->stream) != hipSuccess)
-                    return fail(HMPC_EDEVICE, "fleet: cannot allocate the prediction buffer");
-                HIPCHK(hipMemcpyAsync(f->h_bits, f->ppool + f->used * d.n_primal, B * d.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+            if (f->digest) {
+                // the digest kernel behind the QP kernel; one block comes back: 32 + 8 ceil(nfix / 64) bytes per node.  The cutoff
+                // is decided on the host, at consumption (null here: +inf); the -inf of a weak node's dual objective is written there
+                const size_t words = (size_t)(nfix + 63) / 64;
+                const FleetDigest L = fleet_digest_layout(B, words);
+                char *dd = f->d_digest, *hd = f->h_digest;
+                hmpc_branch_out bo{};
+                bo.obj = (double *)(dd + L.obj); bo.child_lb2 = (double *)(dd + L.lb2); bo.word = (int32_t *)(dd + L.word); bo.pos = (int32_t *)(dd + L.pos);
+                if (ex.dive) bo.bits = (uint64_t *)(dd + L.bits);
+                if ((rc = hmpc_branch_batch_device(h, f->d_fix, (int32_t)B, &r, nullptr, 0, 1, &bo, f->stream))) return rc;
+                HIPCHK(hipMemcpyAsync(hd, dd, L.bytes, hipMemcpyDeviceToHost, f->stream));
+                HIPCHK(hipStreamSynchronize(f->stream));
+                phase.next(f->t_consume);
+                f->rounds++;
+                f->launched += (long long)B;
+                const int handed = fleet_record_round_digest(f->trees, launch, d, (int32_t)f->used, B, f->h_fix, (const double *)(hd + L.obj), (const int32_t *)(hd + L.word),
+                                                             (const int32_t *)(hd + L.pos), (const double *)(hd + L.lb2),
+                                                             ex.dive ? (const uint64_t *)(hd + L.bits) : nullptr, words);
+                if (handed < 0) return fleet_fail(f, HMPC_EDEVICE, "fleet: the digest's pos of a node is not the depth it was launched with");
+                f->handed += handed;
+                f->used += B;
+            } else {
+                HIPCHK(hipMemcpyAsync(f->h_obj, f->d_obj, B * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+                HIPCHK(hipMemcpyAsync(f->h_status, f->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+                HIPCHK(hipMemcpyAsync(f->h_iters, f->d_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+                if (ex.dive) { // the round's primal rows: the rounded binaries of its vertex nodes predict their descendants' dives
+                    if (f->h_bits.grow(B * d.n_primal, 2 * B * d.n_primal, f->stream) != hipSuccess)
+                        return fail(HMPC_EDEVICE, "fleet: cannot allocate the prediction buffer");
+                    HIPCHK(hipMemcpyAsync(f->h_bits, f->ppool + f->used * d.n_primal, B * d.n_primal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+                }
+                HIPCHK(hipMemcpy2DAsync(f->h_nu, 2 * nfix * sizeof(double), rows + d.o_lb, d.n_dual * sizeof(double), 2 * nfix * sizeof(double), B,
+                                        hipMemcpyDeviceToHost, f->stream));
+                HIPCHK(hipStreamSynchronize(f->stream));
+                phase.next(f->t_consume);
+                f->rounds++;
+                f->launched += (long long)B;
+                weak.clear();
+                f->handed += fleet_record_round(f->trees, launch, d, (int32_t)f->used, B, f->h_fix, f->h_obj, f->h_status, f->h_iters, f->h_nu, 2 * (size_t)nfix,
+                                                ex.dive ? (const double *)f->h_bits : nullptr, d.n_primal, weak);
+                for (int32_t q : weak) { // (infeasible, but the ray is no proof to tolerance: the shift must reopen the leaf)
+                    const double ninf = -std::numeric_limits<double>::infinity();
+                    HIPCHK(hipMemcpy(f->dobj[f->cur] + f->used + q, &ninf, sizeof(double), hipMemcpyHostToDevice));
+                }
+                f->used += B;
             }
-            HIPCHK(hipMemcpy2DAsync(f->h_nu, 2 * nfix * sizeof(double), rows + d.o_lb, d.n_dual * sizeof(double), 2 * nfix * sizeof(double), B,
-                                    hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipStreamSynchronize(f->stream));
-            phase.next(f->t_consume);
-            f->rounds++;
-            f->launched += (long long)B;
-            weak.clear();
-            f->handed += fleet_record_round(f->trees, launch, d, (int32_t)f->used, B, f->h_fix, f->h_obj, f->h_status, f->h_iters, f->h_nu, 2 * (size_t)nfix,
-                                            ex.dive ? (const double *)f->h_bits : nullptr, d.n_primal, weak);
-            for (int32_t q : weak) { // (infeasible, but the ray is no proof to tolerance: the shift must reopen the leaf)
-                const double ninf = -std::numeric_limits<double>::infinity();
-                HIPCHK(hipMemcpy(f->dobj[f->cur] + f->used + q, &ninf, sizeof(double), hipMemcpyHostToDevice));
-            }
-            f->used += B;
         }
         // prune / incumbent / branch, node by node in selection order (branch_and_bound.py:476-489)
         for (int k = 0; k < K; k++) {
@@ -389,6 +436,15 @@ extern "C" int hmpc_fleet_timing(const hmpc_fleet *f, double *seconds5)
 {
     if (!f || !seconds5) return fail(HMPC_EINVAL, "fleet: null");
     seconds5[0] = f->t_select; seconds5[1] = f->t_stage; seconds5[2] = f->t_device; seconds5[3] = f->t_consume; seconds5[4] = f->t_shift;
+    return HMPC_OK;
+}
+
+// A round's results through the digest kernel (hmpc_branch.hip) and one copy, instead of three arrays, a strided copy of the
+// multipliers' rows, the primal rows (dive prediction) and one blocking copy per weak node.  Off by default.
+extern "C" int hmpc_fleet_digest(hmpc_fleet *f, int32_t enable)
+{
+    if (!f) return fail(HMPC_EINVAL, "fleet: null");
+    if (enable >= 0) f->digest = enable != 0;
     return HMPC_OK;
 }
 

@@ -33,6 +33,8 @@ struct FleetResult { // a solved node waiting to be consumed by the search (spec
     bool vertex;              // optimal and polished: its record may be handed down to its children (hmpc_warm)
     bool failed;              // the solver did not converge on it (MAXITER / NUMERICAL): an error IF the search consumes it
     bool uncertified = false; // infeasible on the collapse of tau alone, no ray even loosely verified (HMPC_ITERS_UNCERTIFIED)
+    bool digested = false;    // recorded from the device's digest (fleet_record_round_digest): the children's bounds were added there ...
+    double child_lb[2] = {0.0, 0.0}; // ... obj + nu_ub (0-branch), obj + nu_lb (1-branch), the same float64 additions
 };
 
 struct FleetTree {
@@ -172,7 +174,7 @@ inline int tree_consume(FleetTree &t, const std::vector<int> &picks, int nfix, d
                 t.fix.resize((c + 1) * nfix);
                 std::memcpy(t.fix.data() + c * nfix, t.fix.data() + (size_t)i * nfix, nfix);
                 t.fix[c * nfix + d] = (int8_t)v;
-                t.lb.push_back(obj + (v == 1 ? e.nu_lb : e.nu_ub));
+                t.lb.push_back(e.digested ? e.child_lb[v] : obj + (v == 1 ? e.nu_lb : e.nu_ub));
                 t.row.push_back(e.row);
                 t.wrow.push_back(e.vertex ? e.row : -1);
                 t.alive.push_back(1);
@@ -336,6 +338,34 @@ inline int fleet_record_round(std::vector<FleetTree> &trees, const std::vector<F
             const double *u = primal + q * primal_stride + (size_t)(d.T + 1) * d.nx;
             for (int j = 0; j < d.nfix; j++) bits[j] = u[(j / d.nub) * d.nu + d.nuc + (j % d.nub)] > 0.5 ? 1 : 0;
             t.rounded.emplace(e.row, std::move(bits));
+        }
+        t.cache.emplace(tree_key(fix + q * d.nfix, dep), e);
+    }
+    return handed;
+}
+
+// The same from the device's digest of the round (hmpc_branch.hip, the definitions of hmpc_branch.h) instead of the records:
+// node q's objective obj[q], word[q] (HMPC_BRANCH_* of include/hmpc.h: what status and the flags of iters said), pos[q] (the
+// number of its fixed binaries: the identifiers of a fleet are chronological prefixes), lb2 + 2 q: the bounds of its two children
+// (0-branch first), bits + q * words: its rounded relaxed binaries, one bit each -- null without dive prediction.  No list
+// of weak nodes: the digest kernel has written their dual objectives.  Returns the number of nodes whose handed-down active set
+// verified, or -1 if the device's pos of a node is not the depth the host launched it with (nothing is recorded from there on).
+inline int fleet_record_round_digest(std::vector<FleetTree> &trees, const std::vector<FleetLaunch> &launch, const FleetDims &d, int32_t row0, size_t B,
+                                     const int8_t *fix, const double *obj, const int32_t *word, const int32_t *pos, const double *lb2,
+                                     const uint64_t *bits, size_t words)
+{
+    int handed = 0;
+    for (size_t q = 0; q < B; q++) {
+        const int dep = launch[q].depth;
+        if (pos[q] != dep) return -1;
+        handed += (word[q] & HMPC_BRANCH_HANDED) != 0;
+        FleetTree &t = trees[launch[q].k];
+        FleetResult e{obj[q], 0.0, 0.0, row0 + (int32_t)q, (word[q] & HMPC_BRANCH_VERTEX) != 0, (word[q] & HMPC_BRANCH_FAILED) != 0,
+                      (word[q] & HMPC_BRANCH_UNCERTIFIED) != 0, true, {lb2[2 * q], lb2[2 * q + 1]}};
+        if (bits && e.vertex && dep < d.nfix) {
+            std::vector<int8_t> rounded(d.nfix);
+            for (int j = 0; j < d.nfix; j++) rounded[j] = (int8_t)((bits[q * words + j / 64] >> (j % 64)) & 1);
+            t.rounded.emplace(e.row, std::move(rounded));
         }
         t.cache.emplace(tree_key(fix + q * d.nfix, dep), e);
     }

@@ -15,8 +15,12 @@ import numpy as np
 
 class FleetMPC(object):
 
-    def __init__(self, controller, K, handdown=True):
-        """handdown: children solved in a later round than their parent receive the parent's record (``hmpc_warm``: the
+    def __init__(self, controller, K, handdown=True, digest=False):
+        """digest: a round's results come back as the digest of ``hmpc_branch_batch`` -- objective, word, pos, the two child
+        bounds and, with dive prediction, the rounded binaries: one copy of 32 + 8 ceil(T nub / 64) bytes per node -- instead
+        of objective, status, iters, a strided row of multipliers and (dive prediction) the primal row; same results, bit for
+        bit (``hmpc_fleet_digest``; off by default).
+        handdown: children solved in a later round than their parent receive the parent's record (``hmpc_warm``: the
         parent's active set is tried before the first interior-point iteration; the reference hands down the simplex
         basis, controller.py:260-264)."""
         qp = controller.qp
@@ -29,6 +33,8 @@ class FleetMPC(object):
         self._f = ctypes.c_void_p()
         qp._check(qp.lib.hmpc_fleet_create(qp.handle, self.K, ctypes.byref(self._f)))
         qp._check(qp.lib.hmpc_fleet_handdown(self._f, int(bool(handdown)), None))
+        self.digest = bool(digest)
+        qp._check(qp.lib.hmpc_fleet_digest(self._f, int(self.digest)))
 
     def __del__(self):
         f = getattr(self, '_f', None)

@@ -52,6 +52,27 @@ class _CertTol(ctypes.Structure):
     _fields_ = [(k, ctypes.c_double) for k in ('polished', 'unpolished', 'infeasible', 'weak')]
 
 
+class _BranchOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('obj', 'word', 'pos', 'child_lb2', 'bits', 'child_offset', 'n_children',
+                                               'child_fix', 'child_lb', 'child_parent', 'child_warm')]
+
+
+# members of hmpc_branch_out, and the bits of its word (HMPC_BRANCH_* of include/hmpc.h)
+BRANCH_OUTPUTS = tuple(k for k, _ in _BranchOut._fields_)
+BRANCH_FLAGS = dict(branched=0x01, complete=0x02, pruned=0x04, infeasible=0x08, failed=0x10,
+                    vertex=0x100, weak=0x200, uncertified=0x400, handed=0x800)
+
+
+def iters_word(rec):
+    """The ``iters`` word of the C ABI from a record dict of ``solve_batch``, which splits its flags off (polished, weak,
+    handed, second, uncertified); a dict without those keys carries the word as it is."""
+    iters = np.asarray(rec['iters']).astype(np.int64)
+    for key, bit in (('polished', 0x10000), ('weak', 0x20000), ('handed', 0x40000), ('second', 0x80000), ('uncertified', 0x100000)):
+        if rec.get(key) is not None:
+            iters = (iters & ~bit) | np.where(np.asarray(rec[key]) > 0, bit, 0)
+    return np.ascontiguousarray(iters, dtype=np.int32)
+
+
 # columns of hmpc_certify_batch's residual matrix (HMPC_CERT_* of include/hmpc.h) and the classes of its verdict's low byte
 CERT_COLUMNS = ('stationarity', 'sign', 'dual_obj', 'primal_equality', 'primal_inequality', 'obj', 'gap',
                 'ray_quadratic', 'ray_objective', 'ray_primal')
@@ -103,6 +124,13 @@ def load_library():
                                            ctypes.POINTER(_Result), ctypes.POINTER(_CertTol), ctypes.c_void_p, ctypes.c_void_p]
         lib.hmpc_certify_batch_device.restype = ctypes.c_int
         lib.hmpc_certify_batch_device.argtypes = lib.hmpc_certify_batch.argtypes + [ctypes.c_void_p]
+        lib.hmpc_branch_batch.restype = ctypes.c_int
+        lib.hmpc_branch_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(_Result), ctypes.c_void_p,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_BranchOut)]
+        lib.hmpc_branch_batch_device.restype = ctypes.c_int
+        lib.hmpc_branch_batch_device.argtypes = lib.hmpc_branch_batch.argtypes + [ctypes.c_void_p]
+        lib.hmpc_fleet_digest.restype = ctypes.c_int
+        lib.hmpc_fleet_digest.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         lib.hmpc_fleet_create.restype = ctypes.c_int
         lib.hmpc_fleet_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
         lib.hmpc_fleet_destroy.restype = ctypes.c_int
@@ -149,6 +177,7 @@ def load_library():
 EXPORTED_SYMBOLS = ('hmpc_create', 'hmpc_destroy', 'hmpc_record_sizes', 'hmpc_launch_info', 'hmpc_kernel_info', 'hmpc_kernel_recipe', 'hmpc_jit_stats', 'hmpc_jit_build_problem', 'hmpc_validate_kernels', 'hmpc_second_opinion_review',
                     'hmpc_solve_batch', 'hmpc_solve_batch_device', 'hmpc_last_error',
                     'hmpc_set_shift_maps', 'hmpc_shift_batch', 'hmpc_shift_batch_device', 'hmpc_certify_batch', 'hmpc_certify_batch_device',
+                    'hmpc_branch_batch', 'hmpc_branch_batch_device', 'hmpc_fleet_digest',
                     'hmpc_fleet_create', 'hmpc_fleet_destroy', 'hmpc_fleet_reset', 'hmpc_fleet_stop', 'hmpc_fleet_rows', 'hmpc_fleet_solve', 'hmpc_fleet_shift',
                     'hmpc_fleet_stats', 'hmpc_fleet_uncertified', 'hmpc_fleet_handdown', 'hmpc_fleet_timing', 'hmpc_comm_unique_id', 'hmpc_comm_create', 'hmpc_allreduce_incumbent', 'hmpc_allreduce_incumbent_device', 'hmpc_publish_incumbent', 'hmpc_comm_destroy',
                     'hmpc_lp_solve_batch')
@@ -529,3 +558,83 @@ class HipBatchedQP(object):
         self._check(self.lib.hmpc_certify_batch_device(self.handle, x0.data_ptr(), stride, fix.data_ptr() if self.nfix else None, B,
                                                        ctypes.byref(res), self._cert_tol(tol), residuals.data_ptr(),
                                                        verdict.data_ptr() if verdict is not None else None, ctypes.c_void_p(stream)))
+
+    # ------------------------------------------------------------------
+    # branching a batch of solved nodes (controller.py:395-429 of the reference) on the device
+    # ------------------------------------------------------------------
+    def branch_batch(self, fix, rec, cutoff=None, warm_base=0, mark_weak=False, want=None):
+        """The children of a batch of solved nodes, with their lower bounds (``hmpc_branch_batch``; host arrays in and out).
+
+        fix : int8 (B, T*nub);  rec : a dict as ``solve_batch`` returns it (obj, status, iters, primal, dual; dual_obj with
+        ``mark_weak``);  cutoff : optional (B,), a node whose objective is not below it is pruned;  warm_base : row of node 0 in
+        the arrays the next solve is handed (``child_warm`` = warm_base + parent, -1 where the parent is no vertex);
+        want : names of ``BRANCH_OUTPUTS`` to compute (default: all; the others are passed as NULL and are absent).
+        Returns a dict of numpy arrays: obj, word (``BRANCH_FLAGS``), pos, child_lb2 (B, 2), bits (B, ceil(T*nub / 64)) uint64,
+        child_offset, n_children (int), and the children, cut to n_children rows: child_fix, child_lb, child_parent,
+        child_warm; with ``mark_weak`` also dual_obj, -inf on the weak nodes."""
+        fix = np.ascontiguousarray(fix, dtype=np.int8)
+        if fix.ndim != 2 or fix.shape[1] != self.nfix:
+            raise ValueError('fix must have shape (B, %d).' % self.nfix)
+        B = fix.shape[0]
+        want = BRANCH_OUTPUTS if want is None else tuple(want)
+        if set(want) - set(BRANCH_OUTPUTS):
+            raise ValueError('want: unknown outputs %s' % sorted(set(want) - set(BRANCH_OUTPUTS)))
+        keep = dict(obj=np.ascontiguousarray(rec['obj'], dtype=np.float64), status=np.ascontiguousarray(rec['status'], dtype=np.int32),
+                    iters=iters_word(rec))
+        for k, width in (('dual_obj', None), ('primal', self.n_primal), ('dual', self.n_dual)):
+            if rec.get(k) is not None:
+                keep[k] = np.array(rec[k], dtype=np.float64, order='C')     # (a copy: dual_obj is written with mark_weak)
+                if keep[k].shape != ((B,) if width is None else (B, width)):
+                    raise ValueError('record arrays have inconsistent shapes.')
+        if any(keep[k].shape != (B,) for k in ('obj', 'status', 'iters')):
+            raise ValueError('record arrays have inconsistent shapes.')
+        if cutoff is not None:
+            cutoff = np.ascontiguousarray(cutoff, dtype=np.float64)
+            if cutoff.shape != (B,):
+                raise ValueError('cutoff must have shape (B,).')
+        words = (self.nfix + 63) // 64
+        shapes = dict(obj=((B,), np.float64), word=((B,), np.int32), pos=((B,), np.int32), child_lb2=((B, 2), np.float64),
+                      bits=((B, words), np.uint64), child_offset=((B,), np.int32), n_children=((1,), np.int32),
+                      child_fix=((2 * B, self.nfix), np.int8), child_lb=((2 * B,), np.float64),
+                      child_parent=((2 * B,), np.int32), child_warm=((2 * B,), np.int32))
+        out = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in want}
+        r = _Result(**{k: v.ctypes.data for k, v in keep.items()})
+        o = _BranchOut(**{k: v.ctypes.data for k, v in out.items()})
+        self._check(self.lib.hmpc_branch_batch(self.handle, fix.ctypes.data, B, ctypes.byref(r), cutoff.ctypes.data if cutoff is not None else None,
+                                               int(warm_base), int(bool(mark_weak)), ctypes.byref(o)))
+        if 'n_children' in out:
+            out['n_children'] = int(out['n_children'][0])
+            for k in ('child_fix', 'child_lb', 'child_parent', 'child_warm'):
+                if k in out:
+                    out[k] = out[k][:out['n_children']]
+        if mark_weak:
+            out['dual_obj'] = keep['dual_obj']
+        return out
+
+    def branch_batch_device(self, fix, rec, out, cutoff=None, warm_base=0, mark_weak=False, stream=None):
+        """Device-resident form: torch CUDA tensors, asynchronous on ``stream`` (default: torch's current stream).  ``rec`` is
+        the dict ``solve_batch_device`` filled; ``out`` a dict of preallocated tensors under the names of ``BRANCH_OUTPUTS``
+        (missing or None: not wanted) -- obj, child_lb2 [B, 2], child_lb [2B] float64; word, pos, child_offset [B], n_children
+        [1], child_parent, child_warm [2B] int32; bits [B, ceil(T*nub / 64)] int64 (the words' bit patterns); child_fix
+        [2B, T*nub] int8.  A solve, this call, and a solve of ``child_fix[:n_children]`` with ``child_warm`` as the hand-down
+        index run on one stream without a row leaving the device."""
+        import torch
+        B = fix.shape[0]
+        assert fix.dtype == torch.int8 and fix.is_cuda and fix.is_contiguous() and fix.shape[1] == self.nfix
+        dtypes = dict(obj=torch.float64, child_lb2=torch.float64, child_lb=torch.float64, bits=torch.int64, child_fix=torch.int8)
+        ptr = {}
+        for k in BRANCH_OUTPUTS:
+            t = out.get(k)
+            if t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.dtype == dtypes.get(k, torch.int32), k
+                assert t.shape[0] >= (1 if k == 'n_children' else 2 * B if k.startswith('child_') and k not in ('child_lb2', 'child_offset') else B), k
+                ptr[k] = t.data_ptr()
+        for k, dtype in (('obj', torch.float64), ('dual_obj', torch.float64), ('status', torch.int32), ('iters', torch.int32),
+                         ('primal', torch.float64), ('dual', torch.float64)):
+            assert rec.get(k) is None or (rec[k].is_cuda and rec[k].is_contiguous() and rec[k].dtype == dtype and rec[k].shape[0] >= B), k
+        assert cutoff is None or (cutoff.is_cuda and cutoff.is_contiguous() and cutoff.dtype == torch.float64 and cutoff.shape == (B,))
+        r = _Result(**{k: (rec[k].data_ptr() if rec.get(k) is not None else None) for k in ('obj', 'dual_obj', 'status', 'iters', 'primal', 'dual')})
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        self._check(self.lib.hmpc_branch_batch_device(self.handle, fix.data_ptr(), B, ctypes.byref(r), cutoff.data_ptr() if cutoff is not None else None,
+                                                      int(warm_base), int(bool(mark_weak)), ctypes.byref(_BranchOut(**ptr)), ctypes.c_void_p(stream)))
