@@ -1,0 +1,114 @@
+/*
+ * hmpc_search.h -- K branch-and-bound searches whose trees live on the device.
+ *
+ * include/hmpc.h solves, certifies and branches a frontier through device pointers; what was left to the caller is the search
+ * around those calls: which nodes of a tree go next, the incumbent, the tree itself (the reference's loop,
+ * warm_start_hmpc/branch_and_bound.py:462-489; here tree_select / tree_consume of csrc/hmpc_tree.h and _Tree of
+ * warm_start_hmpc_amd/batched.py, both on the host).  An hmpc_search keeps K independent trees in HBM and advances them in
+ * lockstep, one QP launch per round; the host reads back one small word per round, the size of the next launch.
+ *
+ * Per tree the semantics are tree_select + tree_consume without speculation and without dive prediction:
+ *   select   candidates are the nodes with alive && lb < ub - tol; the `width` smallest by (lb, index) are picked, in that
+ *            order (first wins ties; +inf bounds are never picked).  A tree without candidates gets HMPC_SEARCH_DONE, and
+ *            HMPC_SEARCH_INCUMBENT with it if it has an incumbent.  Only trees whose state word is 0 take part.
+ *   consume  pick by pick in selection order, SERIALLY within a tree -- a COMPLETE pick lowers ub and the next pick of the
+ *            same round is compared with the new cutoff.  Node i with record row r:
+ *              status > HMPC_INFEASIBLE: the tree gets HMPC_SEARCH_FAILED and stops; this and its later picks are not consumed
+ *              word = the decision of hmpc_branch_batch for (record, cutoff ub - tol) (csrc/hmpc_branch.h)
+ *              BRANCHED with n + 2 > node_cap: the tree gets HMPC_SEARCH_OVERFLOW and stops, nothing of the pick is written
+ *              solves++; HMPC_ITERS_UNCERTIFIED: uncertified++, unc_lb = min(unc_lb, lb[i]) (the bound BEFORE the solve)
+ *              lb[i] = obj, row[i] = r; HMPC_ITERS_WEAK: dual_obj[r] = -inf (the shift then reopens the leaf)
+ *              PRUNED / INFEASIBLE: the node stays a leaf;  COMPLETE: ub = obj, the node is the incumbent
+ *              BRANCHED: two children are appended, 0-branch first: bound obj + multiplier of the tightened bound, they carry
+ *              row r, and hand row r down if the parent is a VERTEX; the node is no leaf any more
+ * State: every tree owns a slab of node_cap nodes (identifier, bound, row, row to hand down, alive), so that list order is
+ * index order; one pool of row_cap record rows in the layout of hmpc_result holds every solved node; a round's records are
+ * rows row0 .. row0 + B - 1, and row0 advances by B with every consumed round.
+ * The search uses the handle's workspaces through the solve call: at most ONE launch per handle may be in flight.
+ */
+#ifndef HMPC_SEARCH_H
+#define HMPC_SEARCH_H
+
+#include "hmpc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* state word of a tree (0: running) */
+#define HMPC_SEARCH_DONE 0x1      /* no candidate left */
+#define HMPC_SEARCH_INCUMBENT 0x2 /* ... and it has an incumbent */
+#define HMPC_SEARCH_FAILED 0x4    /* a consumed node ended MAXITER / NUMERICAL */
+#define HMPC_SEARCH_OVERFLOW 0x8  /* node_cap */
+
+typedef struct hmpc_search hmpc_search;
+
+/* K trees of node_cap nodes each and one pool of row_cap record rows.  HMPC_EINVAL without touching the GPU: null handle or
+ * out, K, node_cap or row_cap <= 0, a problem without binaries. */
+int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, int32_t row_cap, hmpc_search **out);
+int hmpc_search_destroy(hmpc_search *s);
+
+/* A step begins: x0 (K x nx, host).
+ * count == NULL: every tree is its root (lb = -inf).
+ * Else tree k starts from count[k] leaves, tree by tree: fix (sum x T*nub), lb (sum), and -- where dual != NULL -- their
+ * dual rows (sum x n_dual) and dual objectives (sum), which take the first rows of the pool (leaf j carries row j; nothing
+ * is handed down to it).  A tree with count[k] == 0 has nothing to search: it ends DONE at the first select.
+ * The pool and all counters start from zero.  HMPC_EINVAL: count[k] < 0 or > node_cap, sum(count) beyond the pool with dual. */
+int hmpc_search_begin(hmpc_search *s, const double *x0, const int32_t *count, const int8_t *fix, const double *lb,
+                      const double *dual, const double *dual_obj);
+
+/* One round in two halves, for callers that solve elsewhere and for the tests.
+ * select stages the round and returns its size in *B: the one synchronisation of a round.  width in 1 .. 64.
+ * B = 0: every tree has stopped.
+ * row0 + B > row_cap: HMPC_ETOOBIG with nothing changed. */
+int hmpc_search_select(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t *B, void *stream);
+
+/* Device pointers of the staged round (any pointer NULL: not wanted): B rows of x0 (stride nx) and of identifiers,
+ * the hand-down ready for hmpc_solve_batch_device (rows = the pool's; index[b] = the row node b receives if hand-down was on
+ * at select, else -1), d_rows: the members point at row row0 of the pool, so that hmpc_solve_batch_device writes the records
+ * where consume reads them. */
+int hmpc_search_batch(const hmpc_search *s, const double **d_x0, const int8_t **d_fix, hmpc_warm *d_warm,
+                      hmpc_result *d_rows, int32_t *row0);
+
+/* Host records into the rows of the staged round (an outside solver; the tests' synthetic records).  B: the staged size;
+ * obj, status, iters required, the other members are copied where given. */
+int hmpc_search_put_records(hmpc_search *s, int32_t B, const hmpc_result *host_records);
+
+/* Consumes the staged round.  Asynchronous on `stream`.  HMPC_EINVAL without a staged round. */
+int hmpc_search_consume(hmpc_search *s, double tol, void *stream);
+
+/* select -> hmpc_solve_batch_device -> consume until B == 0 or max_rounds (<= 0: none).  rounds, launched (nullable): QP
+ * launches and nodes of this call.  The states of the trees say how each of them ended (hmpc_search_results). */
+int hmpc_search_run(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t max_rounds, void *stream,
+                    int32_t *rounds, int64_t *launched);
+
+/* Per tree, any pointer NULL.
+ * cost: +inf without incumbent.
+ * u0 (nu), x1 (nx): from the incumbent's primal row, NaN without one.  binaries: the incumbent's identifier, -1 without one.
+ * leaves: alive nodes. */
+int hmpc_search_results(hmpc_search *s, double *cost, double *u0, double *x1, int8_t *binaries /* K x T*nub */,
+                        int32_t *solves, int32_t *leaves, int32_t *state, int32_t *uncertified);
+
+/* The alive nodes of all trees, tree by tree in list order -- the inputs of hmpc_shift_batch.
+ * owner, fix, lb; dual and dual_obj are gathered through `row` (zeros where row < 0).
+ * has_dual: 0 where row < 0.
+ * n: capacity in / count out (HMPC_ETOOBIG with the count in *n when the capacity is short; nothing else is written).
+ * Any of the arrays may be NULL. */
+int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, int8_t *fix, double *lb, double *dual,
+                       double *dual_obj, uint8_t *has_dual);
+
+/* Host copies, for a caller that solves the staged round elsewhere and for inspection (each synchronises; any array NULL).
+ * get_batch: the staged round (B: its size) -- x0 (B x nx), fix (B x T*nub), the rows handed down, and the (tree, node) of
+ *   every pick.
+ * tree: tree k as it stands.  scalars6: n, inc, inc_row, solves, uncertified, state; bounds2: ub, unc_lb; the whole slab,
+ *   node_cap entries each (entries at and beyond n are whatever earlier steps left).
+ * rows: rows first .. first + count - 1 of the pool into (write == 0) or from (write != 0) the host arrays of `host`. */
+int hmpc_search_get_batch(hmpc_search *s, int32_t B, double *x0, int8_t *fix, int32_t *warm, int32_t *tree, int32_t *node);
+int hmpc_search_tree(hmpc_search *s, int32_t k, int32_t *scalars6, double *bounds2, int8_t *fix, double *lb, int32_t *row,
+                     int32_t *wrow, uint8_t *alive);
+int hmpc_search_rows(hmpc_search *s, int32_t first, int32_t count, const hmpc_result *host, int32_t write);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HMPC_SEARCH_H */

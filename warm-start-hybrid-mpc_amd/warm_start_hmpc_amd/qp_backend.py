@@ -170,6 +170,18 @@ def load_library():
         lib.hmpc_lp_solve_batch.argtypes = ([ctypes.c_int32] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32]
                                             + [ctypes.c_void_p] * 5)
+        # the device-resident searches of include/hmpc_search.h
+        vp, i32 = ctypes.c_void_p, ctypes.c_int32
+        for name, args in (('hmpc_search_create', [vp, i32, i32, i32, ctypes.POINTER(vp)]), ('hmpc_search_destroy', [vp]),
+                           ('hmpc_search_begin', [vp] * 7), ('hmpc_search_select', [vp, i32, ctypes.c_double, i32, _ip, vp]),
+                           ('hmpc_search_batch', [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(_Warm), ctypes.POINTER(_Result), _ip]),
+                           ('hmpc_search_put_records', [vp, i32, ctypes.POINTER(_Result)]), ('hmpc_search_consume', [vp, ctypes.c_double, vp]),
+                           ('hmpc_search_run', [vp, i32, ctypes.c_double, i32, i32, vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
+                           ('hmpc_search_results', [vp] * 9), ('hmpc_search_leaves', [vp, _ip] + [vp] * 6),
+                           ('hmpc_search_get_batch', [vp, i32] + [vp] * 5), ('hmpc_search_tree', [vp, i32] + [vp] * 7),
+                           ('hmpc_search_rows', [vp, i32, i32, ctypes.POINTER(_Result), i32])):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = args
         _lib = lib
     return _lib
 
@@ -181,6 +193,12 @@ EXPORTED_SYMBOLS = ('hmpc_create', 'hmpc_destroy', 'hmpc_record_sizes', 'hmpc_la
                     'hmpc_fleet_create', 'hmpc_fleet_destroy', 'hmpc_fleet_reset', 'hmpc_fleet_stop', 'hmpc_fleet_rows', 'hmpc_fleet_solve', 'hmpc_fleet_shift',
                     'hmpc_fleet_stats', 'hmpc_fleet_uncertified', 'hmpc_fleet_handdown', 'hmpc_fleet_timing', 'hmpc_comm_unique_id', 'hmpc_comm_create', 'hmpc_allreduce_incumbent', 'hmpc_allreduce_incumbent_device', 'hmpc_publish_incumbent', 'hmpc_comm_destroy',
                     'hmpc_lp_solve_batch')
+
+# include/hmpc_search.h (a header of its own: include/hmpc.h is part of the key of every compiled kernel)
+EXPORTED_SEARCH_SYMBOLS = ('hmpc_search_create', 'hmpc_search_destroy', 'hmpc_search_begin', 'hmpc_search_select', 'hmpc_search_batch',
+                           'hmpc_search_put_records', 'hmpc_search_consume', 'hmpc_search_run', 'hmpc_search_results', 'hmpc_search_leaves',
+                           'hmpc_search_get_batch', 'hmpc_search_tree', 'hmpc_search_rows')
+SEARCH_STATES = dict(done=0x1, incumbent=0x2, failed=0x4, overflow=0x8)
 
 
 def _problem_struct(problem):

@@ -1,0 +1,255 @@
+"""K branch-and-bound searches whose trees live on the device (``hmpc_search_*``, include/hmpc_search.h).
+
+``BatchedMPC.feedforward_many`` keeps its trees in numpy and ships every round's identifiers, bounds and multipliers across the
+bus; ``FleetMPC`` keeps the multiplier rows in HBM but selects, stages and consumes on the host.  Here the trees, the record
+pool and the three steps around the solve (csrc/hmpc_search.hip) stay on the device: a round reads back one word, the size of
+the next launch.  Per tree the semantics are those of ``_Tree.candidates`` / ``BatchedMPC._consume`` (the reference's
+``branch_and_bound.py:462-489`` with the brancher of ``controller.py:395-429``).
+"""
+import ctypes
+from time import perf_counter
+
+import numpy as np
+
+from .batched import NodeArrays
+from .qp_backend import SEARCH_STATES, _Result, _Warm
+
+
+class SearchTooBig(RuntimeError):
+    """A round's records do not fit the pool (``row_cap``); nothing has changed."""
+
+
+class DeviceSearch(object):
+    """K independent MIQP searches per call, advanced in lockstep on the controller's GPU backend.
+
+    node_cap : nodes a tree may hold (a tree that needs more stops with the OVERFLOW state)
+    row_cap  : rows of the record pool, one per solved node of a step and one per leaf of the covers (default K * node_cap)
+    """
+
+    def __init__(self, controller, K, node_cap=1024, row_cap=None):
+        qp = controller.qp
+        if not hasattr(qp, 'handle') or not hasattr(qp, 'lib'):
+            raise RuntimeError('DeviceSearch needs the HIP backend (the product path has no CPU fallback).')
+        self.c, self.qp, self.K = controller, qp, int(K)
+        self.node_cap = int(node_cap)
+        self.row_cap = int(row_cap) if row_cap is not None else self.K * self.node_cap
+        self.nx, self.nu, self.nfix = qp.nx, qp.nu, qp.nfix
+        self.n_primal, self.n_dual = qp.n_primal, qp.n_dual
+        s = ctypes.c_void_p()
+        rc = qp.lib.hmpc_search_create(qp.handle, self.K, self.node_cap, self.row_cap, ctypes.byref(s))
+        if rc != 0:
+            raise (ValueError if rc == -1 else RuntimeError)('hmpc_search_create failed (%d): %s' % (rc, qp.lib.hmpc_last_error().decode()))
+        self._s = s
+        self.rounds, self.launched = 0, 0
+
+    def __del__(self):
+        s = getattr(self, '_s', None)
+        if s:
+            self.qp.lib.hmpc_search_destroy(s)
+            self._s = None
+
+    def _check(self, rc):
+        if rc == -3:
+            raise SearchTooBig(self.qp.lib.hmpc_last_error().decode())
+        self.qp._check(rc)
+
+    # ------------------------------------------------------------------
+    def begin(self, x0s, warm_starts=None):
+        """A step begins from the states x0s (K, nx).  warm_starts: None (every tree is its root) or a list of K ``NodeArrays``
+        (None entries: the root) whose leaves become the trees, with the dual rows they carry."""
+        x0s = np.ascontiguousarray(np.atleast_2d(x0s), dtype=np.float64)
+        if x0s.shape != (self.K, self.nx):
+            raise ValueError('x0s must have shape (%d, %d).' % (self.K, self.nx))
+        if warm_starts is None:
+            self._check(self.qp.lib.hmpc_search_begin(self._s, x0s.ctypes.data, None, None, None, None, None))
+            return
+        if len(warm_starts) != self.K:
+            raise ValueError('one warm start per tree.')
+        ws = [NodeArrays.root(self.nfix, self.n_dual) if w is None else w for w in warm_starts]
+        count = np.array([len(w) for w in ws], dtype=np.int32)
+        cat = lambda name, dtype: np.ascontiguousarray(np.concatenate([getattr(w, name) for w in ws]), dtype=dtype)
+        fix, lb, dual, dobj = cat('fix', np.int8), cat('lb', np.float64), cat('dual', np.float64), cat('dobj', np.float64)
+        if fix.shape != (count.sum(), self.nfix) or dual.shape != (count.sum(), self.n_dual):
+            raise ValueError('warm starts have inconsistent shapes.')
+        self._check(self.qp.lib.hmpc_search_begin(self._s, x0s.ctypes.data, count.ctypes.data, fix.ctypes.data, lb.ctypes.data,
+                                                  dual.ctypes.data, dobj.ctypes.data))
+
+    def select(self, frontier_width=8, tol=0., handdown=True, stream=None):
+        """Stages the next round and returns its size (0: every tree has stopped) -- the one synchronisation of a round.
+        Raises ``SearchTooBig``, with nothing changed, when the round's records do not fit the pool."""
+        B = ctypes.c_int32()
+        self._check(self.qp.lib.hmpc_search_select(self._s, int(frontier_width), float(tol), int(bool(handdown)), ctypes.byref(B),
+                                                   ctypes.c_void_p(stream)))
+        self._B = B.value
+        return B.value
+
+    def batch(self, device=False):
+        """The staged round.  Host form: dict x0 (B, nx), fix (B, nfix), warm (B: row handed down or -1), tree, node (B), row0.
+        ``device=True``: the raw device pointers instead -- dict x0, fix, warm (primal, dual, index, rows), rows (the six
+        members of ``hmpc_result`` at row0 of the pool), row0 -- ready for ``hmpc_solve_batch_device``."""
+        lib = self.qp.lib
+        if device:
+            x0, fix, warm, rows, row0 = ctypes.c_void_p(), ctypes.c_void_p(), _Warm(), _Result(), ctypes.c_int32()
+            self._check(lib.hmpc_search_batch(self._s, ctypes.byref(x0), ctypes.byref(fix), ctypes.byref(warm), ctypes.byref(rows), ctypes.byref(row0)))
+            return dict(x0=x0.value, fix=fix.value, warm=warm, rows=rows, row0=row0.value)
+        B = self._B
+        row0 = ctypes.c_int32()
+        self._check(lib.hmpc_search_batch(self._s, None, None, None, None, ctypes.byref(row0)))
+        out = dict(x0=np.empty((B, self.nx)), fix=np.empty((B, self.nfix), dtype=np.int8), warm=np.empty(B, dtype=np.int32),
+                   tree=np.empty(B, dtype=np.int32), node=np.empty(B, dtype=np.int32))
+        if B:
+            self._check(lib.hmpc_search_get_batch(self._s, B, *[out[k].ctypes.data for k in ('x0', 'fix', 'warm', 'tree', 'node')]))
+        out['row0'] = row0.value
+        return out
+
+    @staticmethod
+    def _records(rec, B, n_primal, n_dual, empty=False):
+        from .qp_backend import iters_word
+        shapes = dict(obj=((B,), np.float64), dual_obj=((B,), np.float64), status=((B,), np.int32), iters=((B,), np.int32),
+                      primal=((B, n_primal), np.float64), dual=((B, n_dual), np.float64))
+        if empty:
+            keep = {k: np.empty(*v) for k, v in shapes.items()}
+        else:
+            keep = {k: np.ascontiguousarray(iters_word(rec) if k == 'iters' else rec[k], dtype=shapes[k][1])
+                    for k in shapes if k == 'iters' or rec.get(k) is not None}
+            for k, a in keep.items():
+                if a.shape != shapes[k][0]:
+                    raise ValueError('record arrays have inconsistent shapes (%s).' % k)
+        return keep, _Result(**{k: v.ctypes.data for k, v in keep.items()})
+
+    def put_records(self, rec):
+        """Host records (a dict as ``solve_batch`` returns it, or with the ``iters`` word of the C ABI) into the rows of the
+        staged round."""
+        keep, r = self._records(rec, self._B, self.n_primal, self.n_dual)
+        self._check(self.qp.lib.hmpc_search_put_records(self._s, self._B, ctypes.byref(r)))
+
+    def rows(self, first, count, rec=None):
+        """Rows of the pool: read (a dict of arrays, ``iters`` the word of the C ABI) or, with ``rec``, written."""
+        keep, r = self._records(rec, count, self.n_primal, self.n_dual, empty=rec is None)
+        self._check(self.qp.lib.hmpc_search_rows(self._s, int(first), int(count), ctypes.byref(r), int(rec is not None)))
+        return keep
+
+    def consume(self, tol=0., stream=None):
+        self._check(self.qp.lib.hmpc_search_consume(self._s, float(tol), ctypes.c_void_p(stream)))
+        self._B = 0
+
+    def run(self, frontier_width=8, tol=0., handdown=True, max_rounds=0, stream=None):
+        """select -> solve -> consume until every tree has stopped.  Returns (rounds, nodes launched)."""
+        r, n = ctypes.c_int32(), ctypes.c_int64()
+        self._check(self.qp.lib.hmpc_search_run(self._s, int(frontier_width), float(tol), int(bool(handdown)), int(max_rounds),
+                                                ctypes.c_void_p(stream), ctypes.byref(r), ctypes.byref(n)))
+        self.rounds += r.value
+        self.launched += n.value
+        return r.value, n.value
+
+    def results(self):
+        """dict of per-tree arrays: cost (+inf without incumbent), u0 (K, nu), x1 (K, nx) (NaN without one), binaries (K, nfix),
+        solves, leaves, state (``SEARCH_STATES``), uncertified."""
+        K = self.K
+        out = dict(cost=np.empty(K), u0=np.empty((K, self.nu)), x1=np.empty((K, self.nx)), binaries=np.empty((K, self.nfix), dtype=np.int8),
+                   solves=np.empty(K, dtype=np.int32), leaves=np.empty(K, dtype=np.int32), state=np.empty(K, dtype=np.int32),
+                   uncertified=np.empty(K, dtype=np.int32))
+        self._check(self.qp.lib.hmpc_search_results(self._s, *[out[k].ctypes.data for k in ('cost', 'u0', 'x1', 'binaries', 'solves', 'leaves', 'state', 'uncertified')]))
+        return out
+
+    def leaves_flat(self):
+        """The alive nodes of all trees, tree by tree in list order: dict owner, fix, lb, dual, dual_obj, has_dual."""
+        lib = self.qp.lib
+        n = ctypes.c_int32(0)
+        rc = lib.hmpc_search_leaves(self._s, ctypes.byref(n), None, None, None, None, None, None)
+        if rc not in (0, -3):
+            self._check(rc)
+        N = n.value
+        out = dict(owner=np.empty(N, dtype=np.int32), fix=np.empty((N, self.nfix), dtype=np.int8), lb=np.empty(N), dual=np.empty((N, self.n_dual)),
+                   dual_obj=np.empty(N), has_dual=np.empty(N, dtype=np.uint8))
+        self._check(lib.hmpc_search_leaves(self._s, ctypes.byref(n), *[out[k].ctypes.data for k in ('owner', 'fix', 'lb', 'dual', 'dual_obj', 'has_dual')]))
+        assert n.value == N
+        out['has_dual'] = out['has_dual'].astype(bool)
+        return out
+
+    def leaves(self):
+        """One ``NodeArrays`` per tree: its leaves with the dual rows they carry (the warm start's raw material)."""
+        f = self.leaves_flat()
+        out = []
+        for k in range(self.K):
+            m = f['owner'] == k
+            out.append(NodeArrays(f['fix'][m], f['lb'][m], f['dual'][m], f['dual_obj'][m], f['has_dual'][m]))
+        return out
+
+    def tree(self, k):
+        """Tree k as it stands (for inspection): scalars and the whole slab, node_cap entries each."""
+        nc = self.node_cap
+        sc, bd = np.empty(6, dtype=np.int32), np.empty(2)
+        out = dict(fix=np.empty((nc, self.nfix), dtype=np.int8), lb=np.empty(nc), row=np.empty(nc, dtype=np.int32), wrow=np.empty(nc, dtype=np.int32),
+                   alive=np.empty(nc, dtype=np.uint8))
+        self._check(self.qp.lib.hmpc_search_tree(self._s, int(k), sc.ctypes.data, bd.ctypes.data, *[out[q].ctypes.data for q in ('fix', 'lb', 'row', 'wrow', 'alive')]))
+        out.update(zip(('n', 'inc', 'inc_row', 'solves', 'uncertified', 'state'), (int(v) for v in sc)))
+        out.update(ub=bd[0], unc_lb=bd[1])
+        return out
+
+    # ------------------------------------------------------------------
+    def feedforward_many(self, x0s, warm_starts=None, frontier_width=8, tol=0., handdown=True):
+        """Solves K MIQPs; the list of dicts of ``BatchedMPC.feedforward_many`` (objective, ub, x, uc, leaves, solves, time,
+        rounds).  ``x`` holds the two states the search returns (x0 and the model's next state), rows 0 and 1."""
+        x0s = np.atleast_2d(np.asarray(x0s, dtype=np.float64))
+        tic = perf_counter()
+        self.begin(x0s, warm_starts)
+        rounds, _ = self.run(frontier_width, tol, handdown)
+        r = self.results()
+        t = perf_counter() - tic
+        bad = r['state'] & (SEARCH_STATES['failed'] | SEARCH_STATES['overflow'])
+        if np.any(bad & SEARCH_STATES['failed']):
+            raise RuntimeError('QP solver did not converge on a node of %d searches' % int(((bad & SEARCH_STATES['failed']) != 0).sum()))
+        if np.any(bad):
+            raise RuntimeError('%d trees outgrew node_cap = %d' % (int((bad != 0).sum()), self.node_cap))
+        leaves = self.leaves()
+        nub = self.nfix // self.c.layout.T
+        out = []
+        for k in range(self.K):
+            d = dict(objective=float(r['cost'][k]), ub=None, x=None, uc=None, leaves=leaves[k], solves=int(r['solves'][k]), time=t, rounds=rounds)
+            if np.isfinite(r['cost'][k]):
+                ub = r['binaries'][k].reshape(-1, nub).astype(np.float64)
+                ub[0] = r['u0'][k, self.nu - nub:]                 # (stage 0 as the primal row has it: what the shift is given)
+                d.update(x=np.stack((x0s[k], r['x1'][k])), uc=r['u0'][k:k + 1, :self.nu - nub].copy(), ub=ub)
+            out.append(d)
+        return out
+
+    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True):
+        """K closed loops from the same x0 under prescribed model errors (K, n_steps, nx), as ``FleetMPC.closed_loop``: per step
+        ``run``, then the leaves go through the backend's node shift (``hmpc_shift_batch``) and become the covers of ``begin``.
+        A loop whose MIQP is infeasible ends (its tree stays empty).  Returns dict of arrays (K, n_steps): nodes_ws, len_ws,
+        reopened, costs (NaN where a loop has ended), steps, wall."""
+        from .batched import BatchedMPC
+        bm = BatchedMPC(self.c)                                 # (uploads the shift's maps)
+        K = self.K
+        errors = np.asarray(errors, dtype=np.float64)
+        xs = np.repeat(np.asarray(x0, dtype=np.float64)[None], K, axis=0)
+        ws = None
+        alive = np.ones(K, dtype=bool)
+        nothing = NodeArrays(np.zeros((0, self.nfix), np.int8), np.zeros(0), np.zeros((0, self.n_dual)), np.zeros(0), np.zeros(0, bool))
+        stats = dict(nodes_ws=np.zeros((K, n_steps), np.int64), len_ws=np.zeros((K, n_steps), np.int64), reopened=np.zeros((K, n_steps), np.int64),
+                     costs=np.full((K, n_steps), np.nan))
+        tic = perf_counter()
+        steps = 0
+        for t in range(n_steps):
+            if not alive.any():
+                break
+            res = self.feedforward_many(xs, ws, frontier_width, tol, handdown)
+            go = [k for k in range(K) if alive[k] and np.isfinite(res[k]['objective'])]
+            for k in range(K):
+                if alive[k]:
+                    stats['nodes_ws'][k, t] = res[k]['solves']
+            alive[:] = False
+            alive[go] = True
+            ws = [nothing] * K
+            if not go:
+                break
+            new = bm.construct_warm_start_many([res[k]['leaves'] for k in go], xs[go],
+                                               np.array([np.concatenate((res[k]['uc'][0], res[k]['ub'][0])) for k in go]), errors[go, t])
+            for k, w in zip(go, new):
+                ws[k] = w
+                stats['len_ws'][k, t], stats['reopened'][k, t], stats['costs'][k, t] = len(w), int((~w.has_dual).sum()), res[k]['objective']
+                xs[k] = res[k]['x'][1] + errors[k, t]
+                steps += 1
+        stats.update(steps=steps, wall=perf_counter() - tic)
+        return stats
