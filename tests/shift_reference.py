@@ -360,7 +360,7 @@ def dual_objective_property(ctrl, w, ref, got=None, tol=1e-6):
     return lines, worst
 
 
-# ---- dispatch of hmpc_launch_shift (csrc/hmpc_capi.hip), from the layout sizes ---------------------------------------------
+# ---- dispatch of hmpc_launch_shift (csrc/hmpc_shift.hip), from the layout sizes ---------------------------------------------
 SHIFT_WAVES = 4
 
 

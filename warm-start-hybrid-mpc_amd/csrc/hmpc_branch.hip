@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "hmpc_branch.h"
+#include "hmpc_host.h" // the entries at the end of this file: hmpc_handle, the staging table and its transfers
 
 #define BRANCH_WAVES 4          // nodes (waves) per workgroup of the digest and children kernels
 #define BRANCH_SCAN_CHUNK 1024  // nodes per pass of the offsets kernel = its threads
@@ -154,4 +155,91 @@ __global__ void __launch_bounds__(64 * BRANCH_WAVES) hmpc_branch_children_kernel
             if (a.out.child_warm) a.out.child_warm[c] = branch_child_warm(word, a.warm_base, b);
         }
     }
+}
+
+// ---- Host side: the entries of include/hmpc.h (arithmetic: hmpc_branch.h) ------------------------------------------------------
+static BranchDims branch_dims_of(const hmpc_handle *h)
+{
+    const CertProb &c = h->cert; // (the sizes as the caller of hmpc_create stated them)
+    return branch_dims(c.nx, c.nu, c.nub, c.T, c.nc, c.ncL, c.nq, c.nr, c.nqT);
+}
+
+// everything that can be said about the arguments without the device
+static int branch_arguments(const hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *r, int32_t mark_weak, const hmpc_branch_out *out)
+{
+    if (!fix || !r || !out) return fail(HMPC_EINVAL, "branch: null argument (fix, records and out are required)");
+    if (!r->obj || !r->status || !r->iters) return fail(HMPC_EINVAL, "branch: null argument (obj, status and iters of the records are required)");
+    if ((out->child_lb2 || out->child_lb) && !r->dual) return fail(HMPC_EINVAL, "branch: the child bounds need the records' dual rows");
+    if (out->bits && !r->primal) return fail(HMPC_EINVAL, "branch: the rounded bits need the records' primal rows");
+    if (mark_weak && !r->dual_obj) return fail(HMPC_EINVAL, "branch: mark_weak needs the records' dual objectives");
+    if ((out->child_fix || out->child_lb || out->child_parent || out->child_warm) && !out->child_offset)
+        return fail(HMPC_EINVAL, "branch: the child arrays need child_offset");
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (h->cert.nub <= 0) return fail(HMPC_EINVAL, "branch: the problem has no binaries (nub == 0)");
+    if (B > (1 << 30)) return fail(HMPC_EINVAL, "branch: bad batch size (the children of more than 2^30 nodes have no int32 offsets)");
+    return HMPC_OK;
+}
+
+// digest, then -- where asked for -- offsets and children, back to back on `stream`: no allocation, no synchronisation
+static int hmpc_launch_branch(const BranchDims &d, const BranchArgs &a, hipStream_t st)
+{
+    const int need = (a.B + BRANCH_WAVES - 1) / BRANCH_WAVES;
+    const dim3 grid(need < BRANCH_MAX_GRID ? need : BRANCH_MAX_GRID), block(64 * BRANCH_WAVES);
+    const hmpc_branch_out &o = a.out;
+    if (o.obj || o.word || o.pos || o.child_lb2 || o.bits || o.child_offset || a.mark_weak) {
+        hipLaunchKernelGGL(hmpc_branch_digest_kernel, grid, block, 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (o.child_offset || o.n_children) {
+        hipLaunchKernelGGL(hmpc_branch_offsets_kernel, dim3(1), dim3(BRANCH_SCAN_CHUNK), 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (o.child_fix || o.child_lb || o.child_parent || o.child_warm) {
+        hipLaunchKernelGGL(hmpc_branch_children_kernel, grid, block, 0, st, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_branch_batch_device(hmpc_handle *h, const int8_t *d_fix, int32_t B, const hmpc_result *d_records, const double *d_cutoff,
+                                        int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *d_out, void *stream)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of, and nothing is touched: n_children neither)
+    int rc = branch_arguments(h, d_fix, B, d_records, mark_weak, d_out);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const BranchArgs a{B, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters, d_records->primal, d_records->dual,
+                       d_cutoff, warm_base, mark_weak != 0, *d_out};
+    return hmpc_launch_branch(branch_dims_of(h), a, (hipStream_t)stream);
+}
+
+// the handle's two staging blocks (as the host-pointer solve uses them, exact fit): inputs up, outputs down; a part nobody asks for has no bytes
+extern "C" int hmpc_branch_batch(hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *records, const double *cutoff,
+                                 int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *out)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK;
+    int rc = branch_arguments(h, fix, B, records, mark_weak, out);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const StageTable t = stage_branch(stage_dims(h), (size_t)B, fix, *records, cutoff, mark_weak != 0, *out);
+    if ((rc = stage_room(h, t.total, t.total)) || (rc = stage_up(h, t))) return rc;
+    char *hs = h->h_stage, *ds = h->d_stage;
+    const hmpc_branch_out o{t.ptr<double>(BR_O_OBJ, ds), t.ptr<int32_t>(BR_O_WORD, ds), t.ptr<int32_t>(BR_O_POS, ds), t.ptr<double>(BR_O_LB2, ds),
+                            t.ptr<uint64_t>(BR_O_BITS, ds), t.ptr<int32_t>(BR_O_OFFSET, ds), t.ptr<int32_t>(BR_O_N, ds), t.ptr<int8_t>(BR_O_CFIX, ds),
+                            t.ptr<double>(BR_O_CLB, ds), t.ptr<int32_t>(BR_O_CPARENT, ds), t.ptr<int32_t>(BR_O_CWARM, ds)};
+    const BranchArgs a{B, t.ptr<int8_t>(BR_FIX, ds), t.ptr<double>(BR_OBJ, ds), t.ptr<double>(BR_DOBJ, ds), t.ptr<int32_t>(BR_STATUS, ds),
+                       t.ptr<int32_t>(BR_ITERS, ds), t.ptr<double>(BR_PRIMAL, ds), t.ptr<double>(BR_DUAL, ds), t.ptr<double>(BR_CUTOFF, ds), warm_base,
+                       mark_weak != 0, o};
+    if ((rc = hmpc_launch_branch(branch_dims_of(h), a, nullptr)) || (rc = stage_down(h, t, t.total))) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    int32_t nchild = 0;
+    if (t.part[BR_O_N].bytes) std::memcpy(&nchild, hs + t.part[BR_O_N].off, sizeof nchild);
+    if (nchild < 0 || (size_t)nchild > 2 * (size_t)B) return fail(HMPC_EDEVICE, "branch: the device returned a number of children outside [0, 2 B]");
+    // (rows of the child arrays at and beyond n_children are not written: neither on the device nor here)
+    for (int i = t.n_in; i < t.n; i++) t.unpack(hs, i, i >= BR_O_CFIX ? (size_t)nchild : SIZE_MAX);
+    return HMPC_OK;
 }

@@ -20,140 +20,14 @@
 
 #include "hmpc_kernel.hip" // one translation unit: the kernels are launched from this file
 #include "hmpc_jit.h"      // register kernels for shapes without a built-in instantiation, compiled at hmpc_create
-#include "hmpc_shift.hip"
+#include "hmpc_host.h"     // error text, Buffer, hmpc_handle, the transfers of a staging table
+// each family's kernels with its entries (as hmpc_fleet.hip, hmpc_comm.hip and hmpc_lp.hip at the end of this file)
+#include "hmpc_shift.hip"   // the warm-start node shift (hmpc_set_shift_maps, hmpc_shift_batch)
 #include "hmpc_certify.hip" // certificates of a batch of records (hmpc_certify_batch)
 #include "hmpc_branch.hip"  // branching a batch of solved nodes (hmpc_branch_batch)
 #include "hmpc_search.hip"  // the rounds of K device-resident searches (include/hmpc_search.h)
 
 #define HMPC_CHECK_NODES 64 // (even) nodes of the first-use check of a kernel compiled at hmpc_create (hmpc_check_compiled)
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
-#define HIPCHK(call)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(HMPC_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
-// The one owner of device (hipMalloc) and pinned host (hipHostMalloc) memory in this library: a block of size() elements of
-// T, released with its owner.  Converts to T * wherever a raw pointer is read (DevProb, kernel arguments, copies).
-template <class T, bool Pinned>
-class Buffer {
-public:
-    Buffer() = default;
-    Buffer(Buffer &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-    Buffer &operator=(Buffer &&o) noexcept
-    {
-        if (this != &o) { release(); std::swap(p_, o.p_); std::swap(n_, o.n_); }
-        return *this;
-    }
-    Buffer(const Buffer &) = delete;
-    Buffer &operator=(const Buffer &) = delete;
-    ~Buffer() { release(); }
-    operator T *() const { return p_; }
-    size_t size() const { return n_; }
-    void release()
-    {
-        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
-        p_ = nullptr;
-        n_ = 0;
-    }
-    // a new block of n elements in place of the old one (at least one element is allocated: a view of an empty array is not null)
-    hipError_t alloc(size_t n)
-    {
-        release();
-        void *q = nullptr;
-        const size_t bytes = (n ? n : 1) * sizeof(T);
-        const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
-        if (e == hipSuccess) { p_ = (T *)q; n_ = n; }
-        return e;
-    }
-    // Room for `want` elements: a block that is short (or absent) is replaced by one of `cap` elements -- the caller's slack --
-    // once `stream` has finished with it; `keep` leading elements are copied across.
-    hipError_t grow(size_t want, size_t cap, hipStream_t stream, size_t keep = 0)
-    {
-        if (p_ && want <= n_) return hipSuccess;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        if (!p_ || !keep) return alloc(cap);
-        Buffer next;
-        if ((e = next.alloc(cap)) != hipSuccess) return e;
-        if ((e = hipMemcpy(next.p_, p_, keep * sizeof(T), Pinned ? hipMemcpyHostToHost : hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-        *this = std::move(next);
-        return hipSuccess;
-    }
-
-private:
-    T *p_ = nullptr;
-    size_t n_ = 0;
-};
-template <class T> using DevBuf = Buffer<T, false>;
-template <class T> using PinBuf = Buffer<T, true>;
-
-struct hmpc_cfg { // the kernel used for 1 / 2 / 4 waves per node, its LDS carve and resident-node count
-    hmpc_kernel_choice k{};
-    size_t lds = 0;
-    int max_grid = 0;
-    int sized = 0; // k is the run-time-sized kernel compiled with this problem's sizes (hmpc_jit_prepare_sized)
-    int ilp = 0;   // ... with the compiler's ILP schedule: a binary the cache's VALIDATED manifest lists (hmpc_jit.h: sched_flags)
-    // FIRST-USE CHECK of a kernel compiled at hmpc_create: `ref` is the shipped kernel that would serve this wave count without
-    // the run-time compiler; the first launch through this configuration solves its first few nodes with both and compares
-    // statuses and objectives (hmpc_check_compiled).  A kernel that disagrees is dropped for the handle.
-    hmpc_kernel_choice ref{};
-    size_t ref_lds = 0;
-    int ref_grid = 0;
-    int checked = 0; // 0 not yet, 1 agreed, -1 disagreed (ref serves)
-    int second_opinions = 0; // batches with MAXITER / NUMERICAL nodes that the shipped kernel solved again and ended the same way (hmpc_solve_batch_device)
-};
-
-struct hmpc_handle {
-    int device = 0;
-    hmpc_cfg cfg[3];
-    DevProb dp{};               // its pointers are views into the blocks below
-    std::vector<DevBuf<char>> blocks;       // the problem's arrays (hmpc_create)
-    std::vector<DevBuf<char>> shift_blocks; // the shift's maps (hmpc_set_shift_maps; a second call replaces them)
-    const double *shift_MT2 = nullptr;      //   M_mu in pairs of columns, as hmpc_shift_row_kernel keeps it in LDS
-    DevBuf<double> fac_ws;
-    DevBuf<int> work_counter;
-    DevBuf<double> rows_ws;
-    DevBuf<int32_t> order; // processing order of large frontiers (hmpc_order_kernel)
-    DevBuf<int32_t> pend;  // two-launch form of the lazy terminal set: [0] how many nodes wait for their second solve, [1 ..] which
-    DevBuf<char> d_shift;  // staging of the host-pointer shift
-    DevBuf<double> shift_tv; // per tree: what the shift needs of (x0, u0) only (hmpc_shift_tree_kernel)
-    DevBuf<double> cert_mats; // the problem's UNSCALED matrices in one block, in the order of hmpc_problem (hmpc_certify_batch)
-    CertProb cert{};          //   sizes, offsets of the rows and views into that block
-    int cert_form = 0, cert_waves = 4, cert_per_cu = 4, cert_cus = 256; // form of hmpc_certify_kernel, chosen at hmpc_create (hmpc_certify_setup)
-    size_t cert_lds = 0;
-    DevBuf<double> trace;
-    size_t lds = 0;
-    int max_grid = 0, last_grid = 0;
-    // staging for the host-pointer entry point
-    DevBuf<char> d_stage; // one device block (inputs, then outputs: stage_layout)
-    PinBuf<char> h_stage; // its pinned host mirror
-    int last_cfg = -1;            // configuration (0, 1, 2: 1 / 2 / 4 waves per node) of the last launch
-    // SECOND OPINION (hmpc_solve_batch_device): nodes a compiled kernel leaves undecided are listed on the device and solved again
-    // by the shipped kernel in the same stream.  hard: [0] how many of them the shipped kernel leaves undecided too, [1] its work
-    // counter, [2] how many the compiled kernel left, [3 ..] which.  The two counts of the last call travel to h_hard (pinned)
-    // behind hard_done and are looked at when the next call comes, or when a caller that has synchronised asks (hmpc_second_opinion_review).
-    DevBuf<int32_t> hard;
-    PinBuf<int32_t> h_hard;
-    hipEvent_t hard_done = nullptr;
-    int hard_cfg = -1;            // configuration the counts in flight belong to (-1: none)
-    int second_runs = 0;          // calls in which the shipped kernel was asked (for the tests)
-    DevBuf<char> chk;             // device block of the first-use check (check_layout)
-    PinBuf<char> h_chk;           //   its PINNED host mirror (objectives, dual objectives, statuses of the three runs, the hand-down index)
-    int jit_rejected = 0;         //   compiled kernels dropped by it
-    std::vector<void *> jit_libs; // shared objects of kernels compiled for this problem's shape (hmpc_jit.h); never unloaded
-    int jit_kernels = 0;          //   how many of the three wave counts run on such a kernel (hmpc_kernel_info)
-    hmpc_handle() = default;
-    hmpc_handle(const hmpc_handle &) = delete;
-    hmpc_handle &operator=(const hmpc_handle &) = delete;
-    ~hmpc_handle() { if (hard_done) (void)hipEventDestroy(hard_done); }
-};
 
 namespace {
 
@@ -213,23 +87,6 @@ void build_stage(const hmpc_problem &q, const double *F, const double *G, const 
             s.gptr.push_back((int)s.grow.size());
         }
 }
-
-// Host arrays into blocks a handle owns, DevProb's pointers set to them.  After the first failure nothing more is uploaded:
-// rc and hmpc_last_error hold that failure.
-struct Uploader {
-    std::vector<DevBuf<char>> &blocks;
-    int rc = HMPC_OK;
-    template <class T> void operator()(const std::vector<T> &v, const T *&view) { if (rc == HMPC_OK) rc = put(v, view); }
-    template <class T> int put(const std::vector<T> &v, const T *&view)
-    {
-        DevBuf<char> d;
-        HIPCHK(d.alloc((v.size() ? v.size() : 1) * sizeof(T)));
-        if (!v.empty()) HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        view = (const T *)static_cast<char *>(d);
-        blocks.push_back(std::move(d));
-        return HMPC_OK;
-    }
-};
 
 void upload_stage(Uploader &up, const StageHost &s, SparseStage &d)
 {
@@ -297,7 +154,7 @@ bool hmpc_jit_prepare_sized(const DevProb &p, hmpc_cfg (&cfg)[3], std::vector<vo
     hmpc_jit_shape shapes[3];
     int slot[3], count = 0;
     int only = -1;
-    if (const char *e = getenv("HMPC_WAVES")) { const int nw = atoi(e); only = nw == 1 ? 0 : nw == 2 ? 1 : nw == 4 ? 2 : -1; }
+    if (const char *e = getenv("HMPC_WAVES")) { const int nw = atoi(e); only = nw == 1 || nw == 2 || nw == 4 ? hmpc_cfg_index(nw) : -1; }
     for (int c = 0; c < 3; c++) {
         const hmpc_kernel_choice &k = cfg[c].k;
         if (k.kc > 0) {                                                 // register kernel: the static row map with the slots this horizon needs
@@ -387,8 +244,6 @@ static void hmpc_install_backtrace()
 }
 
 namespace {
-
-constexpr size_t LDS_PER_CU = 160 * 1024;
 
 // The host side of a problem (step (a) of hmpc_create): DevProb's sizes and options -- its pointers stay null -- and every array
 // the kernels read except the caller's own, which setup_device uploads as they are.
@@ -774,7 +629,6 @@ int setup_device(hmpc_handle *h, const HostProblem &hp, const hmpc_problem &q, i
 
 } // namespace
 
-static int hmpc_certify_setup(hmpc_handle *h, int cus);
 
 extern "C" int hmpc_create(const hmpc_problem *q, const hmpc_options *opt, hmpc_handle **out)
 {
@@ -874,141 +728,6 @@ extern "C" int hmpc_record_sizes(const hmpc_handle *h, int32_t *n_primal, int32_
     if (!h) return fail(HMPC_EINVAL, "null handle");
     if (n_primal) *n_primal = h->dp.n_primal;
     if (n_dual) *n_dual = h->dp.n_dual;
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_set_shift_maps(hmpc_handle *h, const hmpc_shift_maps *m)
-{
-    g_err.clear();
-    if (!h || !m || !m->M_mu || !m->M_rho || !m->V) return fail(HMPC_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->device));
-    DevProb &p = h->dp;
-    // the retain rule of the shift kernel reads one binary per lane of a wavefront
-    if (p.nub > 64) return fail(HMPC_EINVAL, "the node shift supports at most 64 binaries per stage");
-    // a second call replaces the maps (the previous device copies are released)
-    h->shift_blocks.clear();
-    p.shift_Mmu = p.shift_Mrho = p.shift_V = h->shift_MT2 = nullptr;
-    // M_mu also in pairs of columns: [pair][row] -> (column 2k, column 2k + 1), an odd last column paired with zeros
-    const size_t ncL2 = ((size_t)p.ncL + 1) / 2;
-    std::vector<double> mt(2 * ncL2 * p.nc, 0.0);
-    for (int r = 0; r < p.nc; r++)
-        for (int k = 0; k < p.ncL; k++) mt[((size_t)(k / 2) * p.nc + r) * 2 + (k & 1)] = m->M_mu[(size_t)r * p.ncL + k];
-    auto vec = [](const double *a, size_t n) { return std::vector<double>(a, a + n); };
-    Uploader up{h->shift_blocks};
-    up(vec(m->M_mu, (size_t)p.nc * p.ncL), p.shift_Mmu);
-    up(vec(m->M_rho, (size_t)p.nq * p.nqT), p.shift_Mrho);
-    up(vec(m->V, (size_t)p.nub * p.nu), p.shift_V);
-    up(mt, h->shift_MT2);
-    return up.rc;
-}
-
-static int hmpc_launch_shift(hmpc_handle *h, const ShiftArgs &a, void *stream);
-
-extern "C" int hmpc_shift_batch_device(hmpc_handle *h, int32_t B, int32_t K, const int32_t *d_owner, const double *d_x0,
-                                       const double *d_u0, const double *d_e0, const int8_t *d_fix, const double *d_lb,
-                                       const double *d_dual, const double *d_dual_obj, int8_t *d_fix_out, double *d_lb_out,
-                                       double *d_dual_out, double *d_dual_obj_out, uint8_t *d_flags, void *stream)
-{
-    g_err.clear();
-    if (!h) return fail(HMPC_EINVAL, "null handle");
-    if (!h->dp.shift_Mmu) return fail(HMPC_EINVAL, "hmpc_set_shift_maps has not been called");
-    if (B < 0 || K < 1) return fail(HMPC_EINVAL, "bad leaf or tree count");
-    if (B == 0) return HMPC_OK;
-    if (!d_owner || !d_x0 || !d_u0 || !d_e0 || !d_fix || !d_lb || !d_dual || !d_dual_obj || !d_fix_out || !d_lb_out ||
-        !d_dual_out || !d_dual_obj_out || !d_flags)
-        return fail(HMPC_EINVAL, "null argument");
-    if (d_dual == d_dual_out || d_fix == d_fix_out) return fail(HMPC_EINVAL, "the shift is not in place");
-    HIPCHK(hipSetDevice(h->device));
-    ShiftArgs a{B, K, d_owner, d_x0, d_u0, d_e0, d_fix, d_lb, d_dual, d_dual_obj, nullptr, d_fix_out, d_lb_out, d_dual_out, d_dual_obj_out, d_flags};
-    return hmpc_launch_shift(h, a, stream);
-}
-
-// (shared with the fleet driver, which passes a row indirection)
-static int hmpc_launch_shift(hmpc_handle *h, const ShiftArgs &a, void *stream)
-{
-    const int B = a.B;
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    {   // rows staged in LDS by the memory pipeline (hmpc_shift.hip, second kernel): one workgroup per CU, a row buffer per wave
-        const char *rows_env = getenv("HMPC_SHIFT_ROWS");   // (read per launch: the tests run both kernels in one process)
-        const bool off = rows_env && atoi(rows_env) == 0;
-        static const int cap = getenv("HMPC_SHIFT_ROW_WAVES") ? atoi(getenv("HMPC_SHIFT_ROW_WAVES")) : 0;   // (diagnostic)
-        const size_t fixed = hmpc_shift_row_fixed_doubles(h->dp), per = hmpc_shift_row_wave_doubles(h->dp), room = 160 * 1024 / sizeof(double);
-        int waves = fixed < room ? (int)((room - fixed) / per) : 0;
-        if (waves > 16) waves = 16;
-        if (cap > 0 && cap < waves) waves = cap;
-        const DevProb &q = h->dp;
-        if (!off && h->shift_MT2 && waves >= 4 && q.n_dual >= 2 && q.nub >= 1 && q.nc >= 1 && q.ncL >= 1 && q.nq >= 1 && q.nr >= 1 && q.nx >= 1) {
-            const size_t lds = (fixed + (size_t)waves * per) * sizeof(double), need_tv = (size_t)a.K * hmpc_shift_tree_doubles(q);
-            HIPCHK(h->shift_tv.grow(need_tv, need_tv, (hipStream_t)stream)); // (with the number of trees: the stream's earlier launches still read the old block)
-            int grid = cus > 0 ? cus : 256;
-            const int need = (B + waves - 1) / waves;
-            if (grid > need) grid = need;
-            if (hipFuncSetAttribute((const void *)hmpc_shift_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) {
-                hipLaunchKernelGGL(hmpc_shift_tree_kernel, dim3(a.K), dim3(64), 0, (hipStream_t)stream, h->dp, a.K, a.x0, a.u0, h->shift_tv);
-                hipLaunchKernelGGL(hmpc_shift_row_kernel, dim3(grid), dim3(64 * waves), lds, (hipStream_t)stream, h->dp, a, (const double *)h->shift_tv, (const double2 *)h->shift_MT2);
-                HIPCHK(hipGetLastError());
-                return HMPC_OK;
-            }
-            (void)hipGetLastError();
-        }
-    }
-    // persistent workgroups: enough to fill the device, each wave walks leaves with stride grid * SHIFT_WAVES
-    const bool staged = hmpc_shift_lds_doubles(h->dp, true) * sizeof(double) <= 64 * 1024;
-    const size_t lds = hmpc_shift_lds_doubles(h->dp, staged) * sizeof(double);
-    int per_cu = (int)((160 * 1024) / (lds > 0 ? lds : 1));
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) return fail(HMPC_ETOOBIG, "the shift's last-stage vectors exceed one CU's LDS");
-    int grid = (cus > 0 ? cus : 256) * per_cu;
-    const int need = (B + SHIFT_WAVES - 1) / SHIFT_WAVES;
-    if (grid > need) grid = need;
-    if (staged) {
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute((const void *)hmpc_shift_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(hmpc_shift_kernel<true>, dim3(grid), dim3(64 * SHIFT_WAVES), lds, (hipStream_t)stream, h->dp, a);
-    } else {
-        hipLaunchKernelGGL(hmpc_shift_kernel<false>, dim3(grid), dim3(64 * SHIFT_WAVES), lds, (hipStream_t)stream, h->dp, a);
-    }
-    HIPCHK(hipGetLastError());
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_shift_batch(hmpc_handle *h, int32_t B, int32_t K, const int32_t *owner, const double *x0, const double *u0,
-                                const double *e0, const int8_t *fix, const double *lb, const double *dual, const double *dual_obj,
-                                int8_t *fix_out, double *lb_out, double *dual_out, double *dual_obj_out, uint8_t *flags)
-{
-    g_err.clear();
-    if (!h) return fail(HMPC_EINVAL, "null handle");
-    if (B < 0 || K < 1) return fail(HMPC_EINVAL, "bad leaf or tree count");
-    if (B == 0) return HMPC_OK;
-    if (!owner || !x0 || !u0 || !e0 || !fix || !lb || !dual || !dual_obj || !fix_out || !lb_out || !dual_out || !dual_obj_out || !flags)
-        return fail(HMPC_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->device));
-    const DevProb &p = h->dp;
-    const size_t nf = (size_t)B * p.T * p.nub, nd = (size_t)B * p.n_dual * sizeof(double), nb = (size_t)B * sizeof(double);
-    // one staging block: inputs then outputs
-    struct Part { size_t bytes; const void *src; void *dst; size_t off; };
-    Part parts[] = {{(size_t)B * 4, owner, nullptr, 0}, {(size_t)K * p.nx * 8, x0, nullptr, 0}, {(size_t)K * p.nu * 8, u0, nullptr, 0},
-                    {(size_t)K * p.nx * 8, e0, nullptr, 0}, {nf, fix, nullptr, 0}, {nb, lb, nullptr, 0}, {nd, dual, nullptr, 0},
-                    {nb, dual_obj, nullptr, 0}, {nf, nullptr, fix_out, 0}, {nb, nullptr, lb_out, 0}, {nd, nullptr, dual_out, 0},
-                    {nb, nullptr, dual_obj_out, 0}, {(size_t)B, nullptr, flags, 0}};
-    size_t total = 0;
-    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
-    HIPCHK(h->d_shift.grow(total, total, nullptr));
-    char *base = (char *)h->d_shift;
-    for (const Part &q : parts)
-        if (q.src) HIPCHK(hipMemcpyAsync(base + q.off, q.src, q.bytes, hipMemcpyHostToDevice, 0));
-    const int rc = hmpc_shift_batch_device(h, B, K, (const int32_t *)(base + parts[0].off), (const double *)(base + parts[1].off),
-                                           (const double *)(base + parts[2].off), (const double *)(base + parts[3].off),
-                                           (const int8_t *)(base + parts[4].off), (const double *)(base + parts[5].off),
-                                           (const double *)(base + parts[6].off), (const double *)(base + parts[7].off),
-                                           (int8_t *)(base + parts[8].off), (double *)(base + parts[9].off),
-                                           (double *)(base + parts[10].off), (double *)(base + parts[11].off),
-                                           (uint8_t *)(base + parts[12].off), nullptr);
-    if (rc != HMPC_OK) return rc;
-    for (const Part &q : parts)
-        if (q.dst) HIPCHK(hipMemcpyAsync(q.dst, base + q.off, q.bytes, hipMemcpyDeviceToHost, 0));
-    HIPCHK(hipStreamSynchronize(0));
     return HMPC_OK;
 }
 
@@ -1165,26 +884,33 @@ extern "C" int hmpc_validate_kernels(hmpc_handle *h, const double *d_x0, int32_t
     return HMPC_OK;
 }
 
+// what can be said about the arguments of a solve before the batch size decides whether anything is done (the hand-down is looked at after it)
+static int solve_arguments(const hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B, const hmpc_result *out)
+{
+    if (!h || !x0 || !fix || !out) return fail(HMPC_EINVAL, "null argument");
+    if (B < 0 || (x0_stride != 0 && x0_stride < h->dp.nx)) return fail(HMPC_EINVAL, "bad batch size or x0 stride");
+    return HMPC_OK;
+}
+static bool warm_without_rows(const hmpc_warm *w) { return w && w->index && (!w->primal || !w->dual); }
+
 extern "C" int hmpc_solve_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_stride, const int8_t *d_fix,
                                        int32_t B, const hmpc_warm *d_warm, const hmpc_result *d_out, void *stream)
 {
     g_err.clear();
-    if (!h || !d_x0 || !d_fix || !d_out) return fail(HMPC_EINVAL, "null argument");
-    if (B < 0 || (x0_stride != 0 && x0_stride < h->dp.nx)) return fail(HMPC_EINVAL, "bad batch size or x0 stride");
+    const int rc0 = solve_arguments(h, d_x0, x0_stride, d_fix, B, d_out);
+    if (rc0) return rc0;
     if (B == 0) return HMPC_OK;
     HIPCHK(hipSetDevice(h->device));
     hmpc_second_opinion_review_impl(h, false);
+    if (warm_without_rows(d_warm)) return fail(HMPC_EINVAL, "hmpc_warm: index without record rows");
     DevOut o{d_out->obj, d_out->dual_obj, d_out->status, d_out->iters, d_out->primal, d_out->dual};
     DevWarm w{nullptr, nullptr, nullptr, nullptr, 0};
-    if (d_warm && d_warm->index) {
-        if (!d_warm->primal || !d_warm->dual) return fail(HMPC_EINVAL, "hmpc_warm: index without record rows");
-        w = DevWarm{d_warm->primal, d_warm->dual, d_warm->index, nullptr, 0};
-    }
+    if (d_warm && d_warm->index) w = DevWarm{d_warm->primal, d_warm->dual, d_warm->index, nullptr, 0};
     int nw = hmpc_waves_for(B, h->cfg[0].max_grid);
     // the streaming form holds one node per CU whatever the number of waves: always spread it over all four SIMDs
     if (h->cfg[2].k.big && !getenv("HMPC_WAVES")) nw = 4;
-    hmpc_cfg &cfm = h->cfg[nw == 1 ? 0 : nw == 2 ? 1 : 2];
-    h->last_cfg = nw == 1 ? 0 : nw == 2 ? 1 : 2;
+    h->last_cfg = hmpc_cfg_index(nw);
+    hmpc_cfg &cfm = h->cfg[h->last_cfg];
     if (!cfm.checked) {
         const int rc = hmpc_check_compiled(h, cfm, d_x0, x0_stride, d_fix, B, (hipStream_t)stream);
         if (rc != HMPC_OK) return rc;
@@ -1266,101 +992,68 @@ extern "C" int hmpc_solve_batch_device(hmpc_handle *h, const double *d_x0, int32
 }
 
 // Staging of the host-pointer entry point: ONE device block and ONE pinned host block, inputs first, then the outputs in
-// the order obj | dual_obj | status | iters | primal | dual -- one copy up, one copy down per call (round 1: two pageable
-// copies up, six down, each its own synchronisation: ~100 us of a 1.4 ms branch-and-bound round).
-struct StageLayout {
-    size_t x0, fix, widx, wprim, wdual, obj, dobj, status, iters, primal, dual, in_bytes, total;
-};
-// nw: parent records handed down with the batch (gathered: one row per node that has one)
-static StageLayout stage_layout(const DevProb &p, size_t B, size_t nw = 0)
-{
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    StageLayout L;
-    L.x0 = 0;
-    L.fix = up(B * p.nx * sizeof(double));
-    L.widx = L.fix + up(B * (size_t)p.T * p.nub + 1);
-    L.wprim = L.widx + (nw ? up(B * sizeof(int32_t)) : 0);
-    L.wdual = L.wprim + up(nw * (size_t)p.n_primal * sizeof(double));
-    L.in_bytes = L.wdual + up(nw * (size_t)p.n_dual * sizeof(double));
-    L.obj = L.in_bytes;
-    L.dobj = L.obj + up(B * sizeof(double));
-    L.status = L.dobj + up(B * sizeof(double));
-    L.iters = L.status + up(B * sizeof(int32_t));
-    L.primal = L.iters + up(B * sizeof(int32_t));
-    L.dual = L.primal + up(B * (size_t)p.n_primal * sizeof(double));
-    L.total = L.dual + up(B * (size_t)p.n_dual * sizeof(double));
-    return L;
-}
-
-// Room in both staging blocks for a batch of B nodes, nw of them with a parent record; a block that is short is replaced by one
+// the order obj | dual_obj | status | iters | primal | dual (hmpc_stage.h: stage_solve) -- one copy up, one copy down per call
+// (round 1: two pageable copies up, six down, each its own synchronisation: ~100 us of a 1.4 ms branch-and-bound round).
+// Room in both blocks for a batch of B nodes, nw of them with a parent record; a block that is short is replaced by one
 // for 64 nodes, or B + B / 4 from 64 on (each with room for a record if any of this batch has one)
 static int ensure_staging(hmpc_handle *h, size_t B, size_t nw)
 {
     const size_t cap = B < 64 ? 64 : B + B / 4;
-    const size_t want = stage_layout(h->dp, B, nw).total, room = stage_layout(h->dp, cap, nw ? cap : 0).total;
-    HIPCHK(h->d_stage.grow(want, room, nullptr));
-    HIPCHK(h->h_stage.grow(want, room, nullptr));
-    return HMPC_OK;
+    const StageDims d = stage_dims(h);
+    return stage_room(h, stage_solve(d, B, nw, nullptr, 0, nullptr, nullptr).total, stage_solve(d, cap, nw ? cap : 0, nullptr, 0, nullptr, nullptr).total);
 }
 
 extern "C" int hmpc_solve_batch(hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B,
                                 const hmpc_warm *warm, const hmpc_result *out)
 {
     g_err.clear();
-    if (!h || !x0 || !fix || !out) return fail(HMPC_EINVAL, "null argument");
-    if (B < 0 || (x0_stride != 0 && x0_stride < h->dp.nx)) return fail(HMPC_EINVAL, "bad batch size or x0 stride");
+    int rc = solve_arguments(h, x0, x0_stride, fix, B, out);
+    if (rc) return rc;
     if (B == 0) return HMPC_OK;
     HIPCHK(hipSetDevice(h->device));
     const DevProb &p = h->dp;
     // parent records handed down: gathered, one row per node that has one (the index is rewritten to the gathered rows)
     size_t nwarm = 0;
-    if (warm && warm->index) {
-        if (!warm->primal || !warm->dual) return fail(HMPC_EINVAL, "hmpc_warm: index without record rows");
+    if (warm_without_rows(warm)) return fail(HMPC_EINVAL, "hmpc_warm: index without record rows");
+    if (warm && warm->index)
         for (int b = 0; b < B; b++) {
             if (warm->index[b] >= warm->rows) return fail(HMPC_EINVAL, "hmpc_warm: index beyond the rows handed in");
             nwarm += warm->index[b] >= 0;
         }
-    }
-    int rc = ensure_staging(h, (size_t)B, nwarm);
-    if (rc) return rc;
+    if ((rc = ensure_staging(h, (size_t)B, nwarm))) return rc;
     // offsets of THIS batch (they always fit the capacity the blocks were allocated for): with the capacity's offsets
     // a small branch-and-bound round after one large call dragged the whole capacity-sized primal region along
-    const StageLayout L = stage_layout(p, (size_t)B, nwarm);
+    const StageTable t = stage_solve(stage_dims(h), (size_t)B, nwarm, x0, (size_t)x0_stride, fix, out);
     char *hs = h->h_stage, *ds = h->d_stage;
-    const size_t nfix = (size_t)p.T * p.nub;
-    if (x0_stride == 0) std::memcpy(hs + L.x0, x0, p.nx * sizeof(double));
-    else
-        for (int b = 0; b < B; b++) std::memcpy(hs + L.x0 + (size_t)b * p.nx * sizeof(double), x0 + (size_t)b * x0_stride, p.nx * sizeof(double));
-    std::memcpy(hs + L.fix, fix, (size_t)B * nfix);
     hmpc_warm dw{nullptr, nullptr, nullptr, 0};
     if (nwarm) {
-        int32_t *idx = (int32_t *)(hs + L.widx);
+        int32_t *idx = t.ptr<int32_t>(SOLVE_WIDX, hs);
+        double *wp = t.ptr<double>(SOLVE_WPRIMAL, hs), *wd = t.ptr<double>(SOLVE_WDUAL, hs);
         size_t q = 0;
         for (int b = 0; b < B; b++) {
             const int32_t r = warm->index[b];
             idx[b] = r >= 0 ? (int32_t)q : -1;
             if (r < 0) continue;
-            std::memcpy(hs + L.wprim + q * p.n_primal * sizeof(double), warm->primal + (size_t)r * p.n_primal, p.n_primal * sizeof(double));
-            std::memcpy(hs + L.wdual + q * p.n_dual * sizeof(double), warm->dual + (size_t)r * p.n_dual, p.n_dual * sizeof(double));
+            std::memcpy(wp + q * p.n_primal, warm->primal + (size_t)r * p.n_primal, p.n_primal * sizeof(double));
+            std::memcpy(wd + q * p.n_dual, warm->dual + (size_t)r * p.n_dual, p.n_dual * sizeof(double));
             q++;
         }
-        dw = hmpc_warm{(const double *)(ds + L.wprim), (const double *)(ds + L.wdual), (const int32_t *)(ds + L.widx), (int32_t)nwarm};
+        dw = hmpc_warm{t.ptr<double>(SOLVE_WPRIMAL, ds), t.ptr<double>(SOLVE_WDUAL, ds), t.ptr<int32_t>(SOLVE_WIDX, ds), (int32_t)nwarm};
     }
-    HIPCHK(hipMemcpyAsync(ds, hs, L.in_bytes, hipMemcpyHostToDevice, nullptr));
-    hmpc_result d{(double *)(ds + L.obj), (double *)(ds + L.dobj), (int32_t *)(ds + L.status), (int32_t *)(ds + L.iters),
-                  out->primal ? (double *)(ds + L.primal) : nullptr, out->dual ? (double *)(ds + L.dual) : nullptr};
-    rc = hmpc_solve_batch_device(h, (const double *)(ds + L.x0), x0_stride == 0 ? 0 : p.nx, (const int8_t *)(ds + L.fix), B,
+    if ((rc = stage_up(h, t))) return rc;
+    const hmpc_result d{t.ptr<double>(SOLVE_OBJ, ds), t.ptr<double>(SOLVE_DOBJ, ds), t.ptr<int32_t>(SOLVE_STATUS, ds), t.ptr<int32_t>(SOLVE_ITERS, ds),
+                        t.ptr<double>(SOLVE_PRIMAL, ds), t.ptr<double>(SOLVE_DUAL, ds)};
+    rc = hmpc_solve_batch_device(h, t.ptr<double>(SOLVE_X0, ds), x0_stride == 0 ? 0 : p.nx, t.at<int8_t>(SOLVE_FIX, ds), B,
                                  nwarm ? &dw : nullptr, &d, nullptr);
     if (rc) return rc;
     // small outputs in one copy through the pinned block; large primal / dual blocks straight into the caller's arrays
     // (a pageable copy is pipelined by the runtime, a detour through the staging block would not be)
-    const size_t pbytes = (size_t)B * p.n_primal * sizeof(double), dbytes = (size_t)B * p.n_dual * sizeof(double);
-    const bool big = pbytes + dbytes > (size_t)4 << 20;
-    const size_t small_end = big ? L.primal : (out->dual ? L.dual + dbytes : out->primal ? L.primal + pbytes : L.primal);
-    HIPCHK(hipMemcpyAsync(hs + L.obj, ds + L.obj, small_end - L.obj, hipMemcpyDeviceToHost, nullptr));
+    const StagePart &pr = t.part[SOLVE_PRIMAL], &du = t.part[SOLVE_DUAL];
+    const bool big = (size_t)B * (p.n_primal + p.n_dual) * sizeof(double) > (size_t)4 << 20;
+    if ((rc = stage_down(h, t, big ? pr.off : du.bytes ? t.end(SOLVE_DUAL) : t.end(SOLVE_PRIMAL)))) return rc;
     if (big) {
-        if (out->primal) HIPCHK(hipMemcpyAsync(out->primal, ds + L.primal, pbytes, hipMemcpyDeviceToHost, nullptr));
-        if (out->dual) HIPCHK(hipMemcpyAsync(out->dual, ds + L.dual, dbytes, hipMemcpyDeviceToHost, nullptr));
+        if (pr.bytes) HIPCHK(hipMemcpyAsync(pr.dst, ds + pr.off, pr.bytes, hipMemcpyDeviceToHost, nullptr));
+        if (du.bytes) HIPCHK(hipMemcpyAsync(du.dst, ds + du.off, du.bytes, hipMemcpyDeviceToHost, nullptr));
     }
     HIPCHK(hipStreamSynchronize(nullptr));
 #ifdef HMPC_CHECK
@@ -1376,14 +1069,7 @@ extern "C" int hmpc_solve_batch(hmpc_handle *h, const double *x0, int32_t x0_str
     }
 #endif
     hmpc_second_opinion_review_impl(h, false); // (the stream is idle: the counts of this call's second opinion have arrived)
-    if (out->obj) std::memcpy(out->obj, hs + L.obj, (size_t)B * sizeof(double));
-    if (out->dual_obj) std::memcpy(out->dual_obj, hs + L.dobj, (size_t)B * sizeof(double));
-    if (out->status) std::memcpy(out->status, hs + L.status, (size_t)B * sizeof(int32_t));
-    if (out->iters) std::memcpy(out->iters, hs + L.iters, (size_t)B * sizeof(int32_t));
-    if (!big) {
-        if (out->primal) std::memcpy(out->primal, hs + L.primal, pbytes);
-        if (out->dual) std::memcpy(out->dual, hs + L.dual, dbytes);
-    }
+    for (int i = SOLVE_OBJ; i <= (big ? SOLVE_ITERS : SOLVE_DUAL); i++) t.unpack(hs, i);
     if (h->trace) {
         std::vector<double> tr(2 * 64 * 8 + 32);
         (void)hipMemcpy(tr.data(), h->trace, tr.size() * sizeof(double), hipMemcpyDeviceToHost);
@@ -1412,605 +1098,6 @@ extern "C" int hmpc_solve_batch(hmpc_handle *h, const double *x0, int32_t x0_str
     return HMPC_OK;
 }
 
-// ---- Certificates of a batch of records (include/hmpc.h; kernel: hmpc_certify.hip, arithmetic: hmpc_certify.h) ----------------
-static int certify_arguments(const void *x0, int32_t x0_stride, int32_t B, const hmpc_result *r, const double *residuals)
-{
-    if (!x0 || !r || !residuals || !r->obj || !r->dual_obj || !r->status || !r->iters || !r->primal || !r->dual)
-        return fail(HMPC_EINVAL, "null argument (all six members of the records are required)");
-    if (x0_stride < 0) return fail(HMPC_EINVAL, "bad x0 stride");
-    return HMPC_OK;
-}
-
-// The form of the kernel for this problem, chosen ONCE at hmpc_create (the launch itself then queries nothing and sets nothing):
-// 2 = rows in LDS where at least four waves' rows fit beside the matrices (one workgroup per CU), 1 = rows in place, matrices in
-// LDS up to 64 KB, 0 = everything in place.  A form whose LDS this device does not grant gives way to the next one HERE, and
-// form 0 needs no grant: a launch never changes form.  The limit on dynamic LDS belongs to the kernel FUNCTION, which every
-// handle of the process shares, so it is set to the most any handle can ask for (form 2: all 160 KB of a CU, form 1: 64 KB of
-// matrices) and never to this handle's own need: a later hmpc_create of a smaller problem leaves an earlier handle's launch its
-// grant.  HMPC_CERTIFY_STAGE = 0 / 1 is a TEST switch, read at hmpc_create only: it caps the form, so that the suite runs all
-// three on problems that would take one.
-static int hmpc_certify_setup(hmpc_handle *h, int cus)
-{
-    const CertProb &c = h->cert;
-    const char *env = getenv("HMPC_CERTIFY_STAGE");
-    const int cap = env ? atoi(env) : 2;
-    const size_t room = 160 * 1024, mats_most = 64 * 1024, mats = cert_matrix_doubles(c) * sizeof(double), per = hmpc_certify_row_doubles(c) * sizeof(double);
-    h->cert_cus = cus > 0 ? cus : 256;
-    h->cert_form = 0; h->cert_waves = CERT_WAVES; h->cert_lds = 0; h->cert_per_cu = 4;
-    if (cap < 1 || mats > mats_most) return HMPC_OK;
-    int waves = cap >= 2 ? (int)((room - mats) / per) : 0;
-    if (waves > CERT_MAX_WAVES) waves = CERT_MAX_WAVES;
-    if (waves >= 4) {
-        const size_t lds = mats + (size_t)waves * per;
-        if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) == hipSuccess) {
-            h->cert_form = 2; h->cert_waves = waves; h->cert_lds = lds; h->cert_per_cu = 1;
-            return HMPC_OK;
-        }
-        (void)hipGetLastError();
-    }
-    if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mats_most) == hipSuccess) {
-        int per_cu = (int)(room / (mats ? mats : 1));
-        h->cert_form = 1; h->cert_lds = mats; h->cert_per_cu = per_cu > 4 ? 4 : per_cu;
-        return HMPC_OK;
-    }
-    (void)hipGetLastError();
-    return HMPC_OK;
-}
-
-static int hmpc_launch_certify(hmpc_handle *h, const CertArgs &a, void *stream)
-{
-    const CertProb &c = h->cert;
-    const hipStream_t st = (hipStream_t)stream;
-    const int waves = h->cert_waves, need = (a.B + waves - 1) / waves, most = h->cert_cus * h->cert_per_cu;
-    const dim3 grid(need < most ? need : most), block(64 * waves);
-    if (h->cert_form == 2) hipLaunchKernelGGL((hmpc_certify_kernel<true, true>), grid, block, h->cert_lds, st, c, a);
-    else if (h->cert_form == 1) hipLaunchKernelGGL((hmpc_certify_kernel<true, false>), grid, block, h->cert_lds, st, c, a);
-    else hipLaunchKernelGGL((hmpc_certify_kernel<false, false>), grid, block, 0, st, c, a);
-    HIPCHK(hipGetLastError());
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_certify_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_stride, const int8_t *d_fix, int32_t B,
-                                         const hmpc_result *d_records, const hmpc_cert_tol *tol, double *d_residuals,
-                                         int32_t *d_verdict, void *stream)
-{
-    g_err.clear();
-    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
-    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
-    int rc = certify_arguments(d_x0, x0_stride, B, d_records, d_residuals);
-    if (rc) return rc;
-    if (!h) return fail(HMPC_EINVAL, "null handle");
-    if (!d_fix && h->cert.nub > 0) return fail(HMPC_EINVAL, "null argument");
-    if (x0_stride != 0 && x0_stride < h->cert.nx) return fail(HMPC_EINVAL, "bad x0 stride");
-    HIPCHK(hipSetDevice(h->device));
-    const CertArgs a{B, x0_stride, d_x0, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters,
-                     d_records->primal, d_records->dual, tol ? *tol : cert_default_tol(), d_residuals, d_verdict};
-    return hmpc_launch_certify(h, a, stream);
-}
-
-extern "C" int hmpc_certify_batch(hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B,
-                                  const hmpc_result *records, const hmpc_cert_tol *tol, double *residuals, int32_t *verdict)
-{
-    g_err.clear();
-    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
-    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
-    int rc = certify_arguments(x0, x0_stride, B, records, residuals);
-    if (rc) return rc;
-    if (!h) return fail(HMPC_EINVAL, "null handle");
-    if (!fix && h->cert.nub > 0) return fail(HMPC_EINVAL, "null argument");
-    if (x0_stride != 0 && x0_stride < h->cert.nx) return fail(HMPC_EINVAL, "bad x0 stride");
-    HIPCHK(hipSetDevice(h->device));
-    const CertProb &c = h->cert;
-    // the handle's two staging blocks (as the host-pointer solve uses them): inputs, then the two outputs
-    const size_t n = (size_t)B, nfix = (size_t)c.T * c.nub;
-    struct Part { size_t bytes; const void *src; size_t off; };
-    Part parts[] = {{(x0_stride ? n : 1) * c.nx * sizeof(double), nullptr, 0}, {n * nfix, fix, 0}, {n * sizeof(double), records->obj, 0},
-                    {n * sizeof(double), records->dual_obj, 0}, {n * sizeof(int32_t), records->status, 0}, {n * sizeof(int32_t), records->iters, 0},
-                    {n * c.n_primal * sizeof(double), records->primal, 0}, {n * c.n_dual * sizeof(double), records->dual, 0},
-                    {n * HMPC_CERT_COUNT * sizeof(double), nullptr, 0}, {n * sizeof(int32_t), nullptr, 0}};
-    size_t total = 0;
-    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
-    const size_t in_bytes = parts[8].off;
-    HIPCHK(h->d_stage.grow(total, total, nullptr));
-    HIPCHK(h->h_stage.grow(total, total, nullptr));
-    char *hs = h->h_stage, *ds = h->d_stage;
-    for (size_t b = 0; b < (x0_stride ? n : 1); b++)
-        std::memcpy(hs + b * c.nx * sizeof(double), x0 + b * (size_t)x0_stride, c.nx * sizeof(double));
-    for (const Part &q : parts)
-        if (q.src && q.bytes) std::memcpy(hs + q.off, q.src, q.bytes);
-    HIPCHK(hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, nullptr));
-    const hmpc_result d{(double *)(ds + parts[2].off), (double *)(ds + parts[3].off), (int32_t *)(ds + parts[4].off),
-                        (int32_t *)(ds + parts[5].off), (double *)(ds + parts[6].off), (double *)(ds + parts[7].off)};
-    rc = hmpc_certify_batch_device(h, (const double *)ds, x0_stride ? c.nx : 0, (const int8_t *)(ds + parts[1].off), B, &d, tol,
-                                   (double *)(ds + parts[8].off), (int32_t *)(ds + parts[9].off), nullptr);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(hs + in_bytes, ds + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    std::memcpy(residuals, hs + parts[8].off, parts[8].bytes);
-    if (verdict) std::memcpy(verdict, hs + parts[9].off, parts[9].bytes);
-    return HMPC_OK;
-}
-
-// ---- Branching a batch of solved nodes (include/hmpc.h; kernels: hmpc_branch.hip, arithmetic: hmpc_branch.h) -------------------
-static BranchDims branch_dims_of(const hmpc_handle *h)
-{
-    const CertProb &c = h->cert; // (the sizes as the caller of hmpc_create stated them)
-    return branch_dims(c.nx, c.nu, c.nub, c.T, c.nc, c.ncL, c.nq, c.nr, c.nqT);
-}
-
-// everything that can be said about the arguments without the device
-static int branch_arguments(const hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *r, int32_t mark_weak, const hmpc_branch_out *out)
-{
-    if (!fix || !r || !out) return fail(HMPC_EINVAL, "branch: null argument (fix, records and out are required)");
-    if (!r->obj || !r->status || !r->iters) return fail(HMPC_EINVAL, "branch: null argument (obj, status and iters of the records are required)");
-    if ((out->child_lb2 || out->child_lb) && !r->dual) return fail(HMPC_EINVAL, "branch: the child bounds need the records' dual rows");
-    if (out->bits && !r->primal) return fail(HMPC_EINVAL, "branch: the rounded bits need the records' primal rows");
-    if (mark_weak && !r->dual_obj) return fail(HMPC_EINVAL, "branch: mark_weak needs the records' dual objectives");
-    if ((out->child_fix || out->child_lb || out->child_parent || out->child_warm) && !out->child_offset)
-        return fail(HMPC_EINVAL, "branch: the child arrays need child_offset");
-    if (!h) return fail(HMPC_EINVAL, "null handle");
-    if (h->cert.nub <= 0) return fail(HMPC_EINVAL, "branch: the problem has no binaries (nub == 0)");
-    if (B > (1 << 30)) return fail(HMPC_EINVAL, "branch: bad batch size (the children of more than 2^30 nodes have no int32 offsets)");
-    return HMPC_OK;
-}
-
-// digest, then -- where asked for -- offsets and children, back to back on `stream`: no allocation, no synchronisation
-static int hmpc_launch_branch(const BranchDims &d, const BranchArgs &a, hipStream_t st)
-{
-    const int need = (a.B + BRANCH_WAVES - 1) / BRANCH_WAVES;
-    const dim3 grid(need < BRANCH_MAX_GRID ? need : BRANCH_MAX_GRID), block(64 * BRANCH_WAVES);
-    const hmpc_branch_out &o = a.out;
-    if (o.obj || o.word || o.pos || o.child_lb2 || o.bits || o.child_offset || a.mark_weak) {
-        hipLaunchKernelGGL(hmpc_branch_digest_kernel, grid, block, 0, st, d, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (o.child_offset || o.n_children) {
-        hipLaunchKernelGGL(hmpc_branch_offsets_kernel, dim3(1), dim3(BRANCH_SCAN_CHUNK), 0, st, d, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (o.child_fix || o.child_lb || o.child_parent || o.child_warm) {
-        hipLaunchKernelGGL(hmpc_branch_children_kernel, grid, block, 0, st, d, a);
-        HIPCHK(hipGetLastError());
-    }
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_branch_batch_device(hmpc_handle *h, const int8_t *d_fix, int32_t B, const hmpc_result *d_records, const double *d_cutoff,
-                                        int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *d_out, void *stream)
-{
-    g_err.clear();
-    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
-    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of, and nothing is touched: n_children neither)
-    int rc = branch_arguments(h, d_fix, B, d_records, mark_weak, d_out);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const BranchArgs a{B, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters, d_records->primal, d_records->dual,
-                       d_cutoff, warm_base, mark_weak != 0, *d_out};
-    return hmpc_launch_branch(branch_dims_of(h), a, (hipStream_t)stream);
-}
-
-extern "C" int hmpc_branch_batch(hmpc_handle *h, const int8_t *fix, int32_t B, const hmpc_result *records, const double *cutoff,
-                                 int32_t warm_base, int32_t mark_weak, const hmpc_branch_out *out)
-{
-    g_err.clear();
-    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
-    if (h && B == 0) return HMPC_OK;
-    int rc = branch_arguments(h, fix, B, records, mark_weak, out);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    const BranchDims d = branch_dims_of(h);
-    const size_t n = (size_t)B, nfix = (size_t)d.nfix;
-    const bool children = out->child_fix || out->child_lb || out->child_parent || out->child_warm;
-    // the handle's two staging blocks (as the host-pointer solve uses them): inputs, then outputs; a part nobody asks for has no bytes
-    enum { P_FIX, P_OBJ, P_STATUS, P_ITERS, P_PRIMAL, P_DUAL, P_CUTOFF, P_DOBJ, O_OBJ, O_WORD, O_POS, O_LB2, O_BITS, O_OFF, O_N, O_CFIX, O_CLB, O_CPAR, O_CWARM, PARTS };
-    struct Part { size_t bytes; const void *src; void *dst; size_t off; };
-    Part parts[PARTS] = {{n * nfix, fix, nullptr, 0},
-                         {n * sizeof(double), records->obj, nullptr, 0},
-                         {n * sizeof(int32_t), records->status, nullptr, 0},
-                         {n * sizeof(int32_t), records->iters, nullptr, 0},
-                         {out->bits ? n * d.n_primal * sizeof(double) : 0, records->primal, nullptr, 0},
-                         {(out->child_lb2 || out->child_lb) ? n * d.n_dual * sizeof(double) : 0, records->dual, nullptr, 0},
-                         {cutoff ? n * sizeof(double) : 0, cutoff, nullptr, 0},
-                         {mark_weak ? n * sizeof(double) : 0, records->dual_obj, records->dual_obj, 0}, // (in and out: first of the outputs)
-                         {out->obj ? n * sizeof(double) : 0, nullptr, out->obj, 0},
-                         {out->word ? n * sizeof(int32_t) : 0, nullptr, out->word, 0},
-                         {out->pos ? n * sizeof(int32_t) : 0, nullptr, out->pos, 0},
-                         {out->child_lb2 ? 2 * n * sizeof(double) : 0, nullptr, out->child_lb2, 0},
-                         {out->bits ? n * d.words * sizeof(uint64_t) : 0, nullptr, out->bits, 0},
-                         {out->child_offset ? n * sizeof(int32_t) : 0, nullptr, out->child_offset, 0},
-                         {(out->n_children || children) ? sizeof(int32_t) : 0, nullptr, out->n_children, 0}, // (the children are copied out up to it)
-                         {out->child_fix ? 2 * n * nfix : 0, nullptr, out->child_fix, 0},
-                         {out->child_lb ? 2 * n * sizeof(double) : 0, nullptr, out->child_lb, 0},
-                         {out->child_parent ? 2 * n * sizeof(int32_t) : 0, nullptr, out->child_parent, 0},
-                         {out->child_warm ? 2 * n * sizeof(int32_t) : 0, nullptr, out->child_warm, 0}};
-    size_t total = 0;
-    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
-    const size_t out_begin = parts[P_DOBJ].off;
-    HIPCHK(h->d_stage.grow(total, total, nullptr));
-    HIPCHK(h->h_stage.grow(total, total, nullptr));
-    char *hs = h->h_stage, *ds = h->d_stage;
-    for (int i = 0; i <= P_DOBJ; i++)
-        if (parts[i].bytes) std::memcpy(hs + parts[i].off, parts[i].src, parts[i].bytes);
-    HIPCHK(hipMemcpyAsync(ds, hs, parts[O_OBJ].off, hipMemcpyHostToDevice, nullptr));
-    auto dev = [&](int i) -> char * { return parts[i].bytes ? ds + parts[i].off : nullptr; };
-    const hmpc_result r{(double *)dev(P_OBJ), (double *)dev(P_DOBJ), (int32_t *)dev(P_STATUS), (int32_t *)dev(P_ITERS), (double *)dev(P_PRIMAL), (double *)dev(P_DUAL)};
-    const hmpc_branch_out o{(double *)dev(O_OBJ), (int32_t *)dev(O_WORD), (int32_t *)dev(O_POS), (double *)dev(O_LB2), (uint64_t *)dev(O_BITS), (int32_t *)dev(O_OFF),
-                            (int32_t *)dev(O_N), (int8_t *)dev(O_CFIX), (double *)dev(O_CLB), (int32_t *)dev(O_CPAR), (int32_t *)dev(O_CWARM)};
-    rc = hmpc_branch_batch_device(h, (const int8_t *)ds, B, &r, (const double *)dev(P_CUTOFF), warm_base, mark_weak, &o, nullptr);
-    if (rc) return rc;
-    if (total > out_begin) HIPCHK(hipMemcpyAsync(hs + out_begin, ds + out_begin, total - out_begin, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    int32_t nchild = 0;
-    if (parts[O_N].bytes) std::memcpy(&nchild, hs + parts[O_N].off, sizeof nchild);
-    if (nchild < 0 || (size_t)nchild > 2 * n) return fail(HMPC_EDEVICE, "branch: the device returned a number of children outside [0, 2 B]");
-    for (int i = P_DOBJ; i < PARTS; i++) {
-        const Part &q = parts[i];
-        if (!q.bytes || !q.dst) continue;
-        // (rows of the child arrays at and beyond n_children are not written: neither on the device nor here)
-        const size_t bytes = i >= O_CFIX ? q.bytes / (2 * n) * (size_t)nchild : q.bytes;
-        std::memcpy(q.dst, hs + q.off, bytes);
-    }
-    return HMPC_OK;
-}
-
-// ---- K searches with their trees on the device (include/hmpc_search.h; kernels: hmpc_search.hip, arithmetic: hmpc_search.h) ----
-struct hmpc_search {
-    hmpc_handle *h = nullptr;
-    BranchDims d{};
-    SearchState v{};       // views into the blocks below
-    DevBuf<int8_t> fix, b_fix;
-    DevBuf<double> lb, td, x0, p_obj, p_dual_obj, p_primal, p_dual, b_x0;
-    DevBuf<int32_t> row, wrow, ti, p_status, p_iters, picks, count, offset, word, b_idx;
-    DevBuf<uint8_t> alive;
-    DevBuf<char> tmp;      // begin's compact trees, the outputs of results and leaves
-    PinBuf<int32_t> h_word;
-    int32_t row0 = 0;      // first pool row of the staged (or next) round
-    int32_t staged = 0;    // size of the staged round, 0: none
-    bool begun = false;
-};
-
-static dim3 search_grid(long long waves)
-{
-    const long long need = (waves + SEARCH_WAVES - 1) / SEARCH_WAVES;
-    return dim3((unsigned)(need < 1 ? 1 : need < SEARCH_MAX_GRID ? need : SEARCH_MAX_GRID));
-}
-
-extern "C" int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, int32_t row_cap, hmpc_search **out)
-{
-    g_err.clear();
-    if (out) *out = nullptr;
-    if (K <= 0 || node_cap <= 0 || row_cap <= 0) return fail(HMPC_EINVAL, "search: K, node_cap and row_cap must be positive");
-    if (!h || !out) return fail(HMPC_EINVAL, "search: null handle or out");
-    if (h->cert.nub <= 0) return fail(HMPC_EINVAL, "search: the problem has no binaries (nub == 0)");
-    if ((long long)K * SEARCH_MAX_WIDTH >= (1ll << 31) || (long long)K * node_cap >= (1ll << 31))
-        return fail(HMPC_EINVAL, "search: K too large (a round's picks and the slabs are indexed with int32)");
-    HIPCHK(hipSetDevice(h->device));
-    std::unique_ptr<hmpc_search> s(new hmpc_search);
-    s->h = h;
-    const BranchDims d = s->d = branch_dims_of(h);
-    const size_t nodes = (size_t)K * node_cap, rows = (size_t)row_cap, k = (size_t)K;
-    const size_t batch = std::min(k * SEARCH_MAX_WIDTH, rows); // (a round that does not fit the pool is not staged)
-    HIPCHK(s->fix.alloc(nodes * d.nfix));
-    HIPCHK(s->lb.alloc(nodes));
-    HIPCHK(s->row.alloc(nodes));
-    HIPCHK(s->wrow.alloc(nodes));
-    HIPCHK(s->alive.alloc(nodes));
-    HIPCHK(s->ti.alloc(6 * k));
-    HIPCHK(s->td.alloc(2 * k));
-    HIPCHK(s->x0.alloc(k * d.nx));
-    HIPCHK(s->p_obj.alloc(rows));
-    HIPCHK(s->p_dual_obj.alloc(rows));
-    HIPCHK(s->p_status.alloc(rows));
-    HIPCHK(s->p_iters.alloc(rows));
-    HIPCHK(s->p_primal.alloc(rows * d.n_primal));
-    HIPCHK(s->p_dual.alloc(rows * d.n_dual));
-    HIPCHK(s->picks.alloc(k * SEARCH_MAX_WIDTH));
-    HIPCHK(s->count.alloc(k));
-    HIPCHK(s->offset.alloc(k));
-    HIPCHK(s->word.alloc(4));
-    HIPCHK(s->h_word.alloc(4));
-    HIPCHK(s->b_fix.alloc(batch * d.nfix));
-    HIPCHK(s->b_x0.alloc(batch * d.nx));
-    HIPCHK(s->b_idx.alloc(3 * batch));
-    int32_t *ti = s->ti;
-    double *td = s->td;
-    int32_t *bi = s->b_idx;
-    s->v = SearchState{K, node_cap, row_cap, s->fix, s->lb, s->row, s->wrow, s->alive, ti, ti + k, ti + 2 * k, ti + 3 * k, ti + 4 * k, ti + 5 * k,
-                       td, td + k, s->x0, s->p_obj, s->p_dual_obj, s->p_status, s->p_iters, s->p_primal, s->p_dual, s->picks, s->count, s->offset, s->word,
-                       s->b_fix, s->b_x0, bi, bi + batch, bi + 2 * batch};
-    *out = s.release();
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_destroy(hmpc_search *s)
-{
-    g_err.clear();
-    if (!s) return HMPC_OK;
-    (void)hipSetDevice(s->h->device);
-    (void)hipDeviceSynchronize();
-    delete s;
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_begin(hmpc_search *s, const double *x0, const int32_t *count, const int8_t *fix, const double *lb, const double *dual,
-                                 const double *dual_obj)
-{
-    g_err.clear();
-    if (!s || !x0) return fail(HMPC_EINVAL, "search: null argument (the search and x0 are required)");
-    const BranchDims &d = s->d;
-    const size_t K = (size_t)s->v.K;
-    std::vector<int32_t> off;
-    size_t total = 0;
-    if (count) {
-        if (!fix || !lb) return fail(HMPC_EINVAL, "search: a cover needs fix and lb");
-        if ((dual != nullptr) != (dual_obj != nullptr)) return fail(HMPC_EINVAL, "search: dual rows and dual objectives go together");
-        off.assign(K + 1, 0);
-        for (size_t k = 0; k < K; k++) {
-            if (count[k] < 0 || count[k] > s->v.node_cap) return fail(HMPC_EINVAL, "search: a tree's cover does not fit its slab (node_cap)");
-            total += (size_t)count[k];
-            if (total > (size_t)s->v.row_cap && dual) return fail(HMPC_EINVAL, "search: the covers' rows do not fit the pool (row_cap)");
-            off[k + 1] = (int32_t)total;
-        }
-    }
-    HIPCHK(hipSetDevice(s->h->device));
-    HIPCHK(hipDeviceSynchronize()); // (a step begins: nothing of the last one is in flight)
-    HIPCHK(hipMemcpy(s->x0, x0, K * d.nx * sizeof(double), hipMemcpyHostToDevice));
-    SearchBegin g{nullptr, nullptr, nullptr, 0};
-    if (count) {
-        const size_t o_fix = (K + 1) * sizeof(int32_t), o_lb = (o_fix + total * d.nfix + 7) / 8 * 8, bytes = o_lb + total * sizeof(double);
-        HIPCHK(s->tmp.grow(bytes, bytes, nullptr));
-        char *t = s->tmp;
-        HIPCHK(hipMemcpy(t, off.data(), o_fix, hipMemcpyHostToDevice));
-        if (total) {
-            HIPCHK(hipMemcpy(t + o_fix, fix, total * d.nfix, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(t + o_lb, lb, total * sizeof(double), hipMemcpyHostToDevice));
-            if (dual) {
-                HIPCHK(hipMemcpy(s->p_dual, dual, total * d.n_dual * sizeof(double), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(s->p_dual_obj, dual_obj, total * sizeof(double), hipMemcpyHostToDevice));
-            }
-        }
-        g = SearchBegin{(const int32_t *)t, (const int8_t *)(t + o_fix), (const double *)(t + o_lb), dual != nullptr};
-    }
-    hipLaunchKernelGGL(hmpc_search_begin_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, g);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(nullptr));
-    s->row0 = dual ? (int32_t)total : 0;
-    s->staged = 0;
-    s->begun = true;
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_select(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t *B, void *stream)
-{
-    g_err.clear();
-    if (width < 1 || width > SEARCH_MAX_WIDTH) return fail(HMPC_EINVAL, "search: width must lie in 1 .. 64");
-    if (!s || !B) return fail(HMPC_EINVAL, "search: null argument (the search and B are required)");
-    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
-    HIPCHK(hipSetDevice(s->h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int hd = handdown != 0;
-    s->staged = 0;
-    hipLaunchKernelGGL(hmpc_search_select_kernel, dim3(s->v.K), dim3(SEARCH_SELECT_THREADS), 0, st, s->d, s->v, (int)width, tol);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hmpc_search_offsets_kernel, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->d, s->v, (int)s->row0, hd);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hmpc_search_stage_kernel, search_grid((long long)s->v.K * width), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, (int)width, hd);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_word, s->word, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int32_t *w = s->h_word;
-    if (w[0] < 0 || (long long)w[0] > (long long)s->v.K * width) return fail(HMPC_EDEVICE, "search: the device returned a round size outside [0, K width]");
-    *B = w[0];
-    if (!w[3]) return fail(HMPC_ETOOBIG, "search: the round's records do not fit the pool (row_cap)");
-    s->staged = w[0];
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_batch(const hmpc_search *s, const double **d_x0, const int8_t **d_fix, hmpc_warm *d_warm, hmpc_result *d_rows, int32_t *row0)
-{
-    g_err.clear();
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    const BranchDims &d = s->d;
-    const SearchState &v = s->v;
-    const size_t r = (size_t)s->row0;
-    if (d_x0) *d_x0 = v.b_x0;
-    if (d_fix) *d_fix = v.b_fix;
-    if (d_warm) *d_warm = hmpc_warm{v.p_primal, v.p_dual, v.b_warm, v.row_cap};
-    if (d_rows) *d_rows = hmpc_result{v.p_obj + r, v.p_dual_obj + r, v.p_status + r, v.p_iters + r, v.p_primal + r * d.n_primal, v.p_dual + r * d.n_dual};
-    if (row0) *row0 = s->row0;
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_put_records(hmpc_search *s, int32_t B, const hmpc_result *rec)
-{
-    g_err.clear();
-    if (!s || !rec) return fail(HMPC_EINVAL, "search: null argument");
-    if (!rec->obj || !rec->status || !rec->iters) return fail(HMPC_EINVAL, "search: obj, status and iters of the records are required");
-    if (s->staged <= 0 || B != s->staged) return fail(HMPC_EINVAL, "search: the records are not those of the staged round (its size is B of hmpc_search_select)");
-    HIPCHK(hipSetDevice(s->h->device));
-    const BranchDims &d = s->d;
-    const size_t r = (size_t)s->row0, n = (size_t)B;
-    HIPCHK(hipMemcpy(s->v.p_obj + r, rec->obj, n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->v.p_status + r, rec->status, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->v.p_iters + r, rec->iters, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (rec->dual_obj) HIPCHK(hipMemcpy(s->v.p_dual_obj + r, rec->dual_obj, n * sizeof(double), hipMemcpyHostToDevice));
-    if (rec->primal) HIPCHK(hipMemcpy(s->v.p_primal + r * d.n_primal, rec->primal, n * d.n_primal * sizeof(double), hipMemcpyHostToDevice));
-    if (rec->dual) HIPCHK(hipMemcpy(s->v.p_dual + r * d.n_dual, rec->dual, n * d.n_dual * sizeof(double), hipMemcpyHostToDevice));
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_consume(hmpc_search *s, double tol, void *stream)
-{
-    g_err.clear();
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    if (s->staged <= 0) return fail(HMPC_EINVAL, "search: no round is staged (hmpc_search_select)");
-    HIPCHK(hipSetDevice(s->h->device));
-    hipLaunchKernelGGL(hmpc_search_consume_kernel, search_grid((long long)s->v.K), dim3(64 * SEARCH_WAVES), 0, (hipStream_t)stream, s->d, s->v, (int)s->row0, tol);
-    HIPCHK(hipGetLastError());
-    s->row0 += s->staged;
-    s->staged = 0;
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_run(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t max_rounds, void *stream, int32_t *rounds, int64_t *launched)
-{
-    g_err.clear();
-    if (rounds) *rounds = 0;
-    if (launched) *launched = 0;
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    for (int32_t r = 0; max_rounds <= 0 || r < max_rounds; r++) {
-        int32_t B = 0;
-        int rc = hmpc_search_select(s, width, tol, handdown, &B, stream);
-        if (rc) return rc;
-        if (B == 0) break;
-        const double *x0;
-        const int8_t *fix;
-        hmpc_warm warm;
-        hmpc_result rows;
-        hmpc_search_batch(s, &x0, &fix, &warm, &rows, nullptr);
-        // (as the host-pointer solve does: the hand-down kernel only where a node of the round receives a record)
-        if ((rc = hmpc_solve_batch_device(s->h, x0, s->d.nx, fix, B, s->h_word[2] ? &warm : nullptr, &rows, stream))) return rc;
-        if ((rc = hmpc_search_consume(s, tol, stream))) return rc;
-        if (rounds) ++*rounds;
-        if (launched) *launched += B;
-    }
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_results(hmpc_search *s, double *cost, double *u0, double *x1, int8_t *binaries, int32_t *solves, int32_t *leaves, int32_t *state,
-                                   int32_t *uncertified)
-{
-    g_err.clear();
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
-    HIPCHK(hipSetDevice(s->h->device));
-    const BranchDims &d = s->d;
-    const size_t K = (size_t)s->v.K;
-    struct Part { size_t bytes; void *dst; size_t off; };
-    Part parts[8] = {{cost ? K * sizeof(double) : 0, cost, 0},           {u0 ? K * d.nu * sizeof(double) : 0, u0, 0},
-                     {x1 ? K * d.nx * sizeof(double) : 0, x1, 0},       {solves ? K * sizeof(int32_t) : 0, solves, 0},
-                     {leaves ? K * sizeof(int32_t) : 0, leaves, 0},     {state ? K * sizeof(int32_t) : 0, state, 0},
-                     {uncertified ? K * sizeof(int32_t) : 0, uncertified, 0}, {binaries ? K * d.nfix : 0, binaries, 0}};
-    size_t total = 0;
-    for (Part &q : parts) { q.off = total; total += (q.bytes + 255) / 256 * 256; }
-    if (!total) return HMPC_OK;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(s->tmp.grow(total, total, nullptr));
-    char *t = s->tmp;
-    auto dev = [&](int i) -> char * { return parts[i].bytes ? t + parts[i].off : nullptr; };
-    const SearchResults r{(double *)dev(0), (double *)dev(1), (double *)dev(2), (int8_t *)dev(7), (int32_t *)dev(3), (int32_t *)dev(4), (int32_t *)dev(5), (int32_t *)dev(6)};
-    hipLaunchKernelGGL(hmpc_search_results_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, r);
-    HIPCHK(hipGetLastError());
-    for (const Part &q : parts)
-        if (q.bytes) HIPCHK(hipMemcpy(q.dst, t + q.off, q.bytes, hipMemcpyDeviceToHost));
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, int8_t *fix, double *lb, double *dual, double *dual_obj, uint8_t *has_dual)
-{
-    g_err.clear();
-    if (!s || !n) return fail(HMPC_EINVAL, "search: null argument (the search and n are required)");
-    if (*n < 0) return fail(HMPC_EINVAL, "search: negative capacity");
-    const size_t K = (size_t)s->v.K;
-    std::vector<int32_t> cnt(K), off(K);
-    int rc = hmpc_search_results(s, nullptr, nullptr, nullptr, nullptr, nullptr, cnt.data(), nullptr, nullptr);
-    if (rc) return rc;
-    long long total = 0;
-    for (size_t k = 0; k < K; k++) { off[k] = (int32_t)total; total += cnt[k]; }
-    const int32_t cap = *n;
-    if (total >= (1ll << 31)) return fail(HMPC_ETOOBIG, "search: more than 2^31 leaves");
-    *n = (int32_t)total;
-    if (total > cap) return fail(HMPC_ETOOBIG, "search: more leaves than the caller's arrays hold (their number is in n)");
-    if (!total) return HMPC_OK;
-    const BranchDims &d = s->d;
-    const size_t N = (size_t)total;
-    struct Part { size_t bytes; void *dst; size_t off; };
-    Part parts[7] = {{K * sizeof(int32_t), nullptr, 0},
-                     {owner ? N * sizeof(int32_t) : 0, owner, 0},
-                     {lb ? N * sizeof(double) : 0, lb, 0},
-                     {dual_obj ? N * sizeof(double) : 0, dual_obj, 0},
-                     {dual ? N * d.n_dual * sizeof(double) : 0, dual, 0},
-                     {fix ? N * d.nfix : 0, fix, 0},
-                     {has_dual ? N : 0, has_dual, 0}};
-    size_t bytes = 0;
-    for (Part &q : parts) { q.off = bytes; bytes += (q.bytes + 255) / 256 * 256; }
-    HIPCHK(s->tmp.grow(bytes, bytes, nullptr));
-    char *t = s->tmp;
-    auto dev = [&](int i) -> char * { return parts[i].bytes ? t + parts[i].off : nullptr; };
-    HIPCHK(hipMemcpy(t, off.data(), K * sizeof(int32_t), hipMemcpyHostToDevice));
-    const SearchLeaves o{(const int32_t *)t, (int32_t *)dev(1), (int8_t *)dev(5), (double *)dev(2), (double *)dev(4), (double *)dev(3), (uint8_t *)dev(6)};
-    hipLaunchKernelGGL(hmpc_search_leaves_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, o);
-    HIPCHK(hipGetLastError());
-    for (int i = 1; i < 7; i++)
-        if (parts[i].bytes) HIPCHK(hipMemcpy(parts[i].dst, t + parts[i].off, parts[i].bytes, hipMemcpyDeviceToHost));
-    return HMPC_OK;
-}
-
-// Host copies of the staged round, of one tree and of pool rows: for a caller that solves elsewhere, and for inspection.
-extern "C" int hmpc_search_get_batch(hmpc_search *s, int32_t B, double *x0, int8_t *fix, int32_t *warm, int32_t *tree, int32_t *node)
-{
-    g_err.clear();
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    if (s->staged <= 0 || B != s->staged) return fail(HMPC_EINVAL, "search: no round of this size is staged");
-    HIPCHK(hipSetDevice(s->h->device));
-    const size_t n = (size_t)B;
-    if (x0) HIPCHK(hipMemcpy(x0, s->v.b_x0, n * s->d.nx * sizeof(double), hipMemcpyDeviceToHost));
-    if (fix) HIPCHK(hipMemcpy(fix, s->v.b_fix, n * s->d.nfix, hipMemcpyDeviceToHost));
-    if (warm) HIPCHK(hipMemcpy(warm, s->v.b_warm, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (tree) HIPCHK(hipMemcpy(tree, s->v.b_tree, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (node) HIPCHK(hipMemcpy(node, s->v.b_node, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_tree(hmpc_search *s, int32_t k, int32_t *scalars6, double *bounds2, int8_t *fix, double *lb, int32_t *row, int32_t *wrow, uint8_t *alive)
-{
-    g_err.clear();
-    if (!s) return fail(HMPC_EINVAL, "search: null search");
-    if (k < 0 || k >= s->v.K) return fail(HMPC_EINVAL, "search: no such tree");
-    HIPCHK(hipSetDevice(s->h->device));
-    HIPCHK(hipDeviceSynchronize());
-    const SearchState &v = s->v;
-    const size_t o = (size_t)k * v.node_cap, n = (size_t)v.node_cap;
-    if (scalars6) {
-        const int32_t *src[6] = {v.n, v.inc, v.inc_row, v.solves, v.uncertified, v.state};
-        for (int i = 0; i < 6; i++) HIPCHK(hipMemcpy(scalars6 + i, src[i] + k, sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (bounds2) {
-        HIPCHK(hipMemcpy(bounds2, v.ub + k, sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(bounds2 + 1, v.unc_lb + k, sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (fix) HIPCHK(hipMemcpy(fix, v.fix + o * s->d.nfix, n * s->d.nfix, hipMemcpyDeviceToHost));
-    if (lb) HIPCHK(hipMemcpy(lb, v.lb + o, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (row) HIPCHK(hipMemcpy(row, v.row + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (wrow) HIPCHK(hipMemcpy(wrow, v.wrow + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (alive) HIPCHK(hipMemcpy(alive, v.alive + o, n, hipMemcpyDeviceToHost));
-    return HMPC_OK;
-}
-
-extern "C" int hmpc_search_rows(hmpc_search *s, int32_t first, int32_t count, const hmpc_result *host, int32_t write)
-{
-    g_err.clear();
-    if (!s || !host) return fail(HMPC_EINVAL, "search: null argument");
-    if (first < 0 || count < 0 || (long long)first + count > s->v.row_cap) return fail(HMPC_EINVAL, "search: rows outside the pool");
-    HIPCHK(hipSetDevice(s->h->device));
-    HIPCHK(hipDeviceSynchronize());
-    const BranchDims &d = s->d;
-    const SearchState &v = s->v;
-    const size_t r = (size_t)first, n = (size_t)count;
-    struct Part { void *host, *dev; size_t bytes; };
-    const Part parts[6] = {{host->obj, v.p_obj + r, n * sizeof(double)},
-                           {host->dual_obj, v.p_dual_obj + r, n * sizeof(double)},
-                           {host->status, v.p_status + r, n * sizeof(int32_t)},
-                           {host->iters, v.p_iters + r, n * sizeof(int32_t)},
-                           {host->primal, v.p_primal + r * d.n_primal, n * d.n_primal * sizeof(double)},
-                           {host->dual, v.p_dual + r * d.n_dual, n * d.n_dual * sizeof(double)}};
-    for (const Part &q : parts) {
-        if (!q.host || !q.bytes) continue;
-        if (write) HIPCHK(hipMemcpy(q.dev, q.host, q.bytes, hipMemcpyHostToDevice));
-        else HIPCHK(hipMemcpy(q.host, q.dev, q.bytes, hipMemcpyDeviceToHost));
-    }
-    return HMPC_OK;
-}
 
 #include "hmpc_fleet.hip" // closed loops in lockstep (same translation unit: uses the launchers above)
 #include "hmpc_comm.hip"  // incumbent all-reduce over RCCL

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "hmpc_certify.h"
+#include "hmpc_host.h" // the entries at the end of this file: hmpc_handle, the staging table and its transfers
 
 #define CERT_WAVES 4       // waves per workgroup of the forms that read rows in place
 #define CERT_MAX_WAVES 16  // ... of the form with rows in LDS (one workgroup per CU)
@@ -124,4 +125,104 @@ __global__ void __launch_bounds__(64 * CERT_MAX_WAVES) hmpc_certify_kernel(const
             __builtin_amdgcn_wave_barrier(); // the next record overwrites the buffers
         }
     }
+}
+
+// ---- Host side: the entries of include/hmpc.h (arithmetic: hmpc_certify.h) -----------------------------------------------------
+// everything that can be said about the arguments without the device (after the batch size, which decides whether they are looked at)
+static int certify_arguments(const hmpc_handle *h, const void *x0, int32_t x0_stride, const void *fix, const hmpc_result *r, const double *residuals)
+{
+    if (!x0 || !r || !residuals || !r->obj || !r->dual_obj || !r->status || !r->iters || !r->primal || !r->dual)
+        return fail(HMPC_EINVAL, "null argument (all six members of the records are required)");
+    if (x0_stride < 0) return fail(HMPC_EINVAL, "bad x0 stride");
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (!fix && h->cert.nub > 0) return fail(HMPC_EINVAL, "null argument");
+    if (x0_stride != 0 && x0_stride < h->cert.nx) return fail(HMPC_EINVAL, "bad x0 stride");
+    return HMPC_OK;
+}
+
+// The form of the kernel for this problem, chosen ONCE at hmpc_create (the launch itself then queries nothing and sets nothing):
+// 2 = rows in LDS where at least four waves' rows fit beside the matrices (one workgroup per CU), 1 = rows in place, matrices in
+// LDS up to 64 KB, 0 = everything in place.  A form whose LDS this device does not grant gives way to the next one HERE, and
+// form 0 needs no grant: a launch never changes form.  The limit on dynamic LDS belongs to the kernel FUNCTION, which every
+// handle of the process shares, so it is set to the most any handle can ask for (form 2: all 160 KB of a CU, form 1: 64 KB of
+// matrices) and never to this handle's own need: a later hmpc_create of a smaller problem leaves an earlier handle's launch its
+// grant.  HMPC_CERTIFY_STAGE = 0 / 1 is a TEST switch, read at hmpc_create only: it caps the form, so that the suite runs all
+// three on problems that would take one.
+static int hmpc_certify_setup(hmpc_handle *h, int cus)
+{
+    const CertProb &c = h->cert;
+    const char *env = getenv("HMPC_CERTIFY_STAGE");
+    const int cap = env ? atoi(env) : 2;
+    const size_t room = LDS_PER_CU, mats_most = 64 * 1024, mats = cert_matrix_doubles(c) * sizeof(double), per = hmpc_certify_row_doubles(c) * sizeof(double);
+    h->cert_cus = cus > 0 ? cus : 256;
+    h->cert_form = 0; h->cert_waves = CERT_WAVES; h->cert_lds = 0; h->cert_per_cu = 4;
+    if (cap < 1 || mats > mats_most) return HMPC_OK;
+    int waves = cap >= 2 ? (int)((room - mats) / per) : 0;
+    if (waves > CERT_MAX_WAVES) waves = CERT_MAX_WAVES;
+    if (waves >= 4) {
+        const size_t lds = mats + (size_t)waves * per;
+        if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) == hipSuccess) {
+            h->cert_form = 2; h->cert_waves = waves; h->cert_lds = lds; h->cert_per_cu = 1;
+            return HMPC_OK;
+        }
+        (void)hipGetLastError();
+    }
+    if (hipFuncSetAttribute((const void *)hmpc_certify_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mats_most) == hipSuccess) {
+        int per_cu = (int)(room / (mats ? mats : 1));
+        h->cert_form = 1; h->cert_lds = mats; h->cert_per_cu = per_cu > 4 ? 4 : per_cu;
+        return HMPC_OK;
+    }
+    (void)hipGetLastError();
+    return HMPC_OK;
+}
+
+static int hmpc_launch_certify(hmpc_handle *h, const CertArgs &a, void *stream)
+{
+    const CertProb &c = h->cert;
+    const hipStream_t st = (hipStream_t)stream;
+    const int waves = h->cert_waves, need = (a.B + waves - 1) / waves, most = h->cert_cus * h->cert_per_cu;
+    const dim3 grid(need < most ? need : most), block(64 * waves);
+    if (h->cert_form == 2) hipLaunchKernelGGL((hmpc_certify_kernel<true, true>), grid, block, h->cert_lds, st, c, a);
+    else if (h->cert_form == 1) hipLaunchKernelGGL((hmpc_certify_kernel<true, false>), grid, block, h->cert_lds, st, c, a);
+    else hipLaunchKernelGGL((hmpc_certify_kernel<false, false>), grid, block, 0, st, c, a);
+    HIPCHK(hipGetLastError());
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_certify_batch_device(hmpc_handle *h, const double *d_x0, int32_t x0_stride, const int8_t *d_fix, int32_t B,
+                                         const hmpc_result *d_records, const hmpc_cert_tol *tol, double *d_residuals,
+                                         int32_t *d_verdict, void *stream)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
+    const int rc = certify_arguments(h, d_x0, x0_stride, d_fix, d_records, d_residuals);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CertArgs a{B, x0_stride, d_x0, d_fix, d_records->obj, d_records->dual_obj, d_records->status, d_records->iters,
+                     d_records->primal, d_records->dual, tol ? *tol : cert_default_tol(), d_residuals, d_verdict};
+    return hmpc_launch_certify(h, a, stream);
+}
+
+// the handle's two staging blocks (as the host-pointer solve uses them, exact fit): the inputs up, the two outputs down
+extern "C" int hmpc_certify_batch(hmpc_handle *h, const double *x0, int32_t x0_stride, const int8_t *fix, int32_t B,
+                                  const hmpc_result *records, const hmpc_cert_tol *tol, double *residuals, int32_t *verdict)
+{
+    g_err.clear();
+    if (B < 0) return fail(HMPC_EINVAL, "bad batch size");
+    if (h && B == 0) return HMPC_OK; // (an empty batch has no arrays to speak of: a view of an empty array may be null)
+    int rc = certify_arguments(h, x0, x0_stride, fix, records, residuals);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const StageTable t = stage_certify(stage_dims(h), (size_t)B, x0, (size_t)x0_stride, fix, *records, residuals, verdict);
+    if ((rc = stage_room(h, t.total, t.total)) || (rc = stage_up(h, t))) return rc;
+    char *ds = h->d_stage;
+    const CertArgs a{B, x0_stride ? h->cert.nx : 0, t.ptr<double>(CERT_X0, ds), t.ptr<int8_t>(CERT_FIX, ds), t.ptr<double>(CERT_OBJ, ds),
+                     t.ptr<double>(CERT_DOBJ, ds), t.ptr<int32_t>(CERT_STATUS, ds), t.ptr<int32_t>(CERT_ITERS, ds), t.ptr<double>(CERT_PRIMAL, ds),
+                     t.ptr<double>(CERT_DUAL, ds), tol ? *tol : cert_default_tol(), t.ptr<double>(CERT_RES, ds), t.ptr<int32_t>(CERT_VERDICT, ds)};
+    if ((rc = hmpc_launch_certify(h, a, nullptr)) || (rc = stage_down(h, t, t.total))) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    t.unpack(h->h_stage, CERT_RES);
+    t.unpack(h->h_stage, CERT_VERDICT);
+    return HMPC_OK;
 }

@@ -21,7 +21,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <memory>
+
 #include "hmpc_search.h"
+#include "hmpc_host.h" // the entries at the end of this file: hmpc_handle (and branch_dims_of, hmpc_branch.hip), the staging table and its transfers
 
 #define SEARCH_WAVES 4             // wavefronts per workgroup of the stage, consume, results and leaves kernels
 #define SEARCH_SELECT_THREADS 256  // threads of a tree's workgroup in select
@@ -272,4 +276,338 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_begin_kernel(co
             s.offset[k] = 0;
         }
     }
+}
+
+// ---- Host side: the entries of include/hmpc_search.h (arithmetic: hmpc_search.h) -----------------------------------------------
+struct hmpc_search {
+    hmpc_handle *h = nullptr;
+    BranchDims d{};
+    SearchState v{};       // views into the blocks below
+    DevBuf<int8_t> fix, b_fix;
+    DevBuf<double> lb, td, x0, p_obj, p_dual_obj, p_primal, p_dual, b_x0;
+    DevBuf<int32_t> row, wrow, ti, p_status, p_iters, picks, count, offset, word, b_idx;
+    DevBuf<uint8_t> alive;
+    DevBuf<char> tmp;      // begin's compact trees, the outputs of results and leaves (hmpc_stage.h; exact fit, one blocking copy per array)
+    PinBuf<int32_t> h_word;
+    int32_t row0 = 0;      // first pool row of the staged (or next) round
+    int32_t staged = 0;    // size of the staged round, 0: none
+    bool begun = false;
+};
+
+static dim3 search_grid(long long waves)
+{
+    const long long need = (waves + SEARCH_WAVES - 1) / SEARCH_WAVES;
+    return dim3((unsigned)(need < 1 ? 1 : need < SEARCH_MAX_GRID ? need : SEARCH_MAX_GRID));
+}
+
+extern "C" int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, int32_t row_cap, hmpc_search **out)
+{
+    g_err.clear();
+    if (out) *out = nullptr;
+    if (K <= 0 || node_cap <= 0 || row_cap <= 0) return fail(HMPC_EINVAL, "search: K, node_cap and row_cap must be positive");
+    if (!h || !out) return fail(HMPC_EINVAL, "search: null handle or out");
+    if (h->cert.nub <= 0) return fail(HMPC_EINVAL, "search: the problem has no binaries (nub == 0)");
+    if ((long long)K * SEARCH_MAX_WIDTH >= (1ll << 31) || (long long)K * node_cap >= (1ll << 31))
+        return fail(HMPC_EINVAL, "search: K too large (a round's picks and the slabs are indexed with int32)");
+    HIPCHK(hipSetDevice(h->device));
+    std::unique_ptr<hmpc_search> s(new hmpc_search);
+    s->h = h;
+    const BranchDims d = s->d = branch_dims_of(h);
+    const size_t nodes = (size_t)K * node_cap, rows = (size_t)row_cap, k = (size_t)K;
+    const size_t batch = std::min(k * SEARCH_MAX_WIDTH, rows); // (a round that does not fit the pool is not staged)
+    HIPCHK(s->fix.alloc(nodes * d.nfix));
+    HIPCHK(s->lb.alloc(nodes));
+    HIPCHK(s->row.alloc(nodes));
+    HIPCHK(s->wrow.alloc(nodes));
+    HIPCHK(s->alive.alloc(nodes));
+    HIPCHK(s->ti.alloc(6 * k));
+    HIPCHK(s->td.alloc(2 * k));
+    HIPCHK(s->x0.alloc(k * d.nx));
+    HIPCHK(s->p_obj.alloc(rows));
+    HIPCHK(s->p_dual_obj.alloc(rows));
+    HIPCHK(s->p_status.alloc(rows));
+    HIPCHK(s->p_iters.alloc(rows));
+    HIPCHK(s->p_primal.alloc(rows * d.n_primal));
+    HIPCHK(s->p_dual.alloc(rows * d.n_dual));
+    HIPCHK(s->picks.alloc(k * SEARCH_MAX_WIDTH));
+    HIPCHK(s->count.alloc(k));
+    HIPCHK(s->offset.alloc(k));
+    HIPCHK(s->word.alloc(4));
+    HIPCHK(s->h_word.alloc(4));
+    HIPCHK(s->b_fix.alloc(batch * d.nfix));
+    HIPCHK(s->b_x0.alloc(batch * d.nx));
+    HIPCHK(s->b_idx.alloc(3 * batch));
+    int32_t *ti = s->ti;
+    double *td = s->td;
+    int32_t *bi = s->b_idx;
+    s->v = SearchState{K, node_cap, row_cap, s->fix, s->lb, s->row, s->wrow, s->alive, ti, ti + k, ti + 2 * k, ti + 3 * k, ti + 4 * k, ti + 5 * k,
+                       td, td + k, s->x0, s->p_obj, s->p_dual_obj, s->p_status, s->p_iters, s->p_primal, s->p_dual, s->picks, s->count, s->offset, s->word,
+                       s->b_fix, s->b_x0, bi, bi + batch, bi + 2 * batch};
+    *out = s.release();
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_destroy(hmpc_search *s)
+{
+    g_err.clear();
+    if (!s) return HMPC_OK;
+    (void)hipSetDevice(s->h->device);
+    (void)hipDeviceSynchronize();
+    delete s;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_begin(hmpc_search *s, const double *x0, const int32_t *count, const int8_t *fix, const double *lb, const double *dual,
+                                 const double *dual_obj)
+{
+    g_err.clear();
+    if (!s || !x0) return fail(HMPC_EINVAL, "search: null argument (the search and x0 are required)");
+    const BranchDims &d = s->d;
+    const size_t K = (size_t)s->v.K;
+    std::vector<int32_t> off;
+    size_t total = 0;
+    if (count) {
+        if (!fix || !lb) return fail(HMPC_EINVAL, "search: a cover needs fix and lb");
+        if ((dual != nullptr) != (dual_obj != nullptr)) return fail(HMPC_EINVAL, "search: dual rows and dual objectives go together");
+        off.assign(K + 1, 0);
+        for (size_t k = 0; k < K; k++) {
+            if (count[k] < 0 || count[k] > s->v.node_cap) return fail(HMPC_EINVAL, "search: a tree's cover does not fit its slab (node_cap)");
+            total += (size_t)count[k];
+            if (total > (size_t)s->v.row_cap && dual) return fail(HMPC_EINVAL, "search: the covers' rows do not fit the pool (row_cap)");
+            off[k + 1] = (int32_t)total;
+        }
+    }
+    HIPCHK(hipSetDevice(s->h->device));
+    HIPCHK(hipDeviceSynchronize()); // (a step begins: nothing of the last one is in flight)
+    HIPCHK(hipMemcpy(s->x0, x0, K * d.nx * sizeof(double), hipMemcpyHostToDevice));
+    SearchBegin g{nullptr, nullptr, nullptr, 0};
+    if (count) {
+        const StageTable t = stage_search_begin(stage_dims(s->h), K, total, off.data(), fix, lb);
+        HIPCHK(s->tmp.grow(t.total, t.total, nullptr));
+        char *base = s->tmp;
+        const int rc = stage_each_up(t, base, false);
+        if (rc) return rc;
+        if (total && dual) {
+            HIPCHK(hipMemcpy(s->p_dual, dual, total * d.n_dual * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(s->p_dual_obj, dual_obj, total * sizeof(double), hipMemcpyHostToDevice));
+        }
+        g = SearchBegin{t.at<int32_t>(SB_OFFSET, base), t.at<int8_t>(SB_FIX, base), t.at<double>(SB_LB, base), dual != nullptr}; // (an empty cover too)
+    }
+    hipLaunchKernelGGL(hmpc_search_begin_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, g);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(nullptr));
+    s->row0 = dual ? (int32_t)total : 0;
+    s->staged = 0;
+    s->begun = true;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_select(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t *B, void *stream)
+{
+    g_err.clear();
+    if (width < 1 || width > SEARCH_MAX_WIDTH) return fail(HMPC_EINVAL, "search: width must lie in 1 .. 64");
+    if (!s || !B) return fail(HMPC_EINVAL, "search: null argument (the search and B are required)");
+    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
+    HIPCHK(hipSetDevice(s->h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int hd = handdown != 0;
+    s->staged = 0;
+    hipLaunchKernelGGL(hmpc_search_select_kernel, dim3(s->v.K), dim3(SEARCH_SELECT_THREADS), 0, st, s->d, s->v, (int)width, tol);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_offsets_kernel, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->d, s->v, (int)s->row0, hd);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_stage_kernel, search_grid((long long)s->v.K * width), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, (int)width, hd);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->h_word, s->word, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int32_t *w = s->h_word;
+    if (w[0] < 0 || (long long)w[0] > (long long)s->v.K * width) return fail(HMPC_EDEVICE, "search: the device returned a round size outside [0, K width]");
+    *B = w[0];
+    if (!w[3]) return fail(HMPC_ETOOBIG, "search: the round's records do not fit the pool (row_cap)");
+    s->staged = w[0];
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_batch(const hmpc_search *s, const double **d_x0, const int8_t **d_fix, hmpc_warm *d_warm, hmpc_result *d_rows, int32_t *row0)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    const BranchDims &d = s->d;
+    const SearchState &v = s->v;
+    const size_t r = (size_t)s->row0;
+    if (d_x0) *d_x0 = v.b_x0;
+    if (d_fix) *d_fix = v.b_fix;
+    if (d_warm) *d_warm = hmpc_warm{v.p_primal, v.p_dual, v.b_warm, v.row_cap};
+    if (d_rows) *d_rows = hmpc_result{v.p_obj + r, v.p_dual_obj + r, v.p_status + r, v.p_iters + r, v.p_primal + r * d.n_primal, v.p_dual + r * d.n_dual};
+    if (row0) *row0 = s->row0;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_put_records(hmpc_search *s, int32_t B, const hmpc_result *rec)
+{
+    g_err.clear();
+    if (!s || !rec) return fail(HMPC_EINVAL, "search: null argument");
+    if (!rec->obj || !rec->status || !rec->iters) return fail(HMPC_EINVAL, "search: obj, status and iters of the records are required");
+    if (s->staged <= 0 || B != s->staged) return fail(HMPC_EINVAL, "search: the records are not those of the staged round (its size is B of hmpc_search_select)");
+    HIPCHK(hipSetDevice(s->h->device));
+    const BranchDims &d = s->d;
+    const size_t r = (size_t)s->row0, n = (size_t)B;
+    HIPCHK(hipMemcpy(s->v.p_obj + r, rec->obj, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->v.p_status + r, rec->status, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->v.p_iters + r, rec->iters, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (rec->dual_obj) HIPCHK(hipMemcpy(s->v.p_dual_obj + r, rec->dual_obj, n * sizeof(double), hipMemcpyHostToDevice));
+    if (rec->primal) HIPCHK(hipMemcpy(s->v.p_primal + r * d.n_primal, rec->primal, n * d.n_primal * sizeof(double), hipMemcpyHostToDevice));
+    if (rec->dual) HIPCHK(hipMemcpy(s->v.p_dual + r * d.n_dual, rec->dual, n * d.n_dual * sizeof(double), hipMemcpyHostToDevice));
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_consume(hmpc_search *s, double tol, void *stream)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (s->staged <= 0) return fail(HMPC_EINVAL, "search: no round is staged (hmpc_search_select)");
+    HIPCHK(hipSetDevice(s->h->device));
+    hipLaunchKernelGGL(hmpc_search_consume_kernel, search_grid((long long)s->v.K), dim3(64 * SEARCH_WAVES), 0, (hipStream_t)stream, s->d, s->v, (int)s->row0, tol);
+    HIPCHK(hipGetLastError());
+    s->row0 += s->staged;
+    s->staged = 0;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_run(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t max_rounds, void *stream, int32_t *rounds, int64_t *launched)
+{
+    g_err.clear();
+    if (rounds) *rounds = 0;
+    if (launched) *launched = 0;
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    for (int32_t r = 0; max_rounds <= 0 || r < max_rounds; r++) {
+        int32_t B = 0;
+        int rc = hmpc_search_select(s, width, tol, handdown, &B, stream);
+        if (rc) return rc;
+        if (B == 0) break;
+        const double *x0;
+        const int8_t *fix;
+        hmpc_warm warm;
+        hmpc_result rows;
+        hmpc_search_batch(s, &x0, &fix, &warm, &rows, nullptr);
+        // (as the host-pointer solve does: the hand-down kernel only where a node of the round receives a record)
+        if ((rc = hmpc_solve_batch_device(s->h, x0, s->d.nx, fix, B, s->h_word[2] ? &warm : nullptr, &rows, stream))) return rc;
+        if ((rc = hmpc_search_consume(s, tol, stream))) return rc;
+        if (rounds) ++*rounds;
+        if (launched) *launched += B;
+    }
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_results(hmpc_search *s, double *cost, double *u0, double *x1, int8_t *binaries, int32_t *solves, int32_t *leaves, int32_t *state,
+                                   int32_t *uncertified)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
+    HIPCHK(hipSetDevice(s->h->device));
+    const BranchDims &d = s->d;
+    const size_t K = (size_t)s->v.K;
+    const StageTable t = stage_search_results(stage_dims(s->h), K, cost, u0, x1, binaries, solves, leaves, state, uncertified);
+    if (!t.total) return HMPC_OK;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(s->tmp.grow(t.total, t.total, nullptr));
+    char *base = s->tmp;
+    const SearchResults r{t.ptr<double>(SR_COST, base), t.ptr<double>(SR_U0, base), t.ptr<double>(SR_X1, base), t.ptr<int8_t>(SR_BINARIES, base),
+                          t.ptr<int32_t>(SR_SOLVES, base), t.ptr<int32_t>(SR_LEAVES, base), t.ptr<int32_t>(SR_STATE, base), t.ptr<int32_t>(SR_UNCERTIFIED, base)};
+    hipLaunchKernelGGL(hmpc_search_results_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, r);
+    HIPCHK(hipGetLastError());
+    return stage_each_down(t, base, false);
+}
+
+extern "C" int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, int8_t *fix, double *lb, double *dual, double *dual_obj, uint8_t *has_dual)
+{
+    g_err.clear();
+    if (!s || !n) return fail(HMPC_EINVAL, "search: null argument (the search and n are required)");
+    if (*n < 0) return fail(HMPC_EINVAL, "search: negative capacity");
+    const size_t K = (size_t)s->v.K;
+    std::vector<int32_t> cnt(K), off(K);
+    int rc = hmpc_search_results(s, nullptr, nullptr, nullptr, nullptr, nullptr, cnt.data(), nullptr, nullptr);
+    if (rc) return rc;
+    long long total = 0;
+    for (size_t k = 0; k < K; k++) { off[k] = (int32_t)total; total += cnt[k]; }
+    const int32_t cap = *n;
+    if (total >= (1ll << 31)) return fail(HMPC_ETOOBIG, "search: more than 2^31 leaves");
+    *n = (int32_t)total;
+    if (total > cap) return fail(HMPC_ETOOBIG, "search: more leaves than the caller's arrays hold (their number is in n)");
+    if (!total) return HMPC_OK;
+    const BranchDims &d = s->d;
+    const StageTable t = stage_search_leaves(stage_dims(s->h), K, (size_t)total, off.data(), owner, fix, lb, dual, dual_obj, has_dual);
+    HIPCHK(s->tmp.grow(t.total, t.total, nullptr));
+    char *base = s->tmp;
+    if ((rc = stage_each_up(t, base, false))) return rc;
+    const SearchLeaves o{t.ptr<int32_t>(SL_OFFSET, base), t.ptr<int32_t>(SL_OWNER, base), t.ptr<int8_t>(SL_FIX, base), t.ptr<double>(SL_LB, base),
+                         t.ptr<double>(SL_DUAL, base), t.ptr<double>(SL_DOBJ, base), t.ptr<uint8_t>(SL_HAS_DUAL, base)};
+    hipLaunchKernelGGL(hmpc_search_leaves_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, o);
+    HIPCHK(hipGetLastError());
+    return stage_each_down(t, base, false);
+}
+
+// Host copies of the staged round, of one tree and of pool rows: for a caller that solves elsewhere, and for inspection.
+extern "C" int hmpc_search_get_batch(hmpc_search *s, int32_t B, double *x0, int8_t *fix, int32_t *warm, int32_t *tree, int32_t *node)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (s->staged <= 0 || B != s->staged) return fail(HMPC_EINVAL, "search: no round of this size is staged");
+    HIPCHK(hipSetDevice(s->h->device));
+    const size_t n = (size_t)B;
+    if (x0) HIPCHK(hipMemcpy(x0, s->v.b_x0, n * s->d.nx * sizeof(double), hipMemcpyDeviceToHost));
+    if (fix) HIPCHK(hipMemcpy(fix, s->v.b_fix, n * s->d.nfix, hipMemcpyDeviceToHost));
+    if (warm) HIPCHK(hipMemcpy(warm, s->v.b_warm, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (tree) HIPCHK(hipMemcpy(tree, s->v.b_tree, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (node) HIPCHK(hipMemcpy(node, s->v.b_node, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_tree(hmpc_search *s, int32_t k, int32_t *scalars6, double *bounds2, int8_t *fix, double *lb, int32_t *row, int32_t *wrow, uint8_t *alive)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (k < 0 || k >= s->v.K) return fail(HMPC_EINVAL, "search: no such tree");
+    HIPCHK(hipSetDevice(s->h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const SearchState &v = s->v;
+    const size_t o = (size_t)k * v.node_cap, n = (size_t)v.node_cap;
+    if (scalars6) {
+        const int32_t *src[6] = {v.n, v.inc, v.inc_row, v.solves, v.uncertified, v.state};
+        for (int i = 0; i < 6; i++) HIPCHK(hipMemcpy(scalars6 + i, src[i] + k, sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (bounds2) {
+        HIPCHK(hipMemcpy(bounds2, v.ub + k, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(bounds2 + 1, v.unc_lb + k, sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (fix) HIPCHK(hipMemcpy(fix, v.fix + o * s->d.nfix, n * s->d.nfix, hipMemcpyDeviceToHost));
+    if (lb) HIPCHK(hipMemcpy(lb, v.lb + o, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (row) HIPCHK(hipMemcpy(row, v.row + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (wrow) HIPCHK(hipMemcpy(wrow, v.wrow + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (alive) HIPCHK(hipMemcpy(alive, v.alive + o, n, hipMemcpyDeviceToHost));
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_rows(hmpc_search *s, int32_t first, int32_t count, const hmpc_result *host, int32_t write)
+{
+    g_err.clear();
+    if (!s || !host) return fail(HMPC_EINVAL, "search: null argument");
+    if (first < 0 || count < 0 || (long long)first + count > s->v.row_cap) return fail(HMPC_EINVAL, "search: rows outside the pool");
+    HIPCHK(hipSetDevice(s->h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const BranchDims &d = s->d;
+    const SearchState &v = s->v;
+    const size_t r = (size_t)first, n = (size_t)count;
+    auto move = [write](void *host, void *dev, size_t bytes) { // (the pool's own arrays: no block, no layout)
+        if (!host || !bytes) return hipSuccess;
+        return write ? hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice) : hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
+    };
+    HIPCHK(move(host->obj, v.p_obj + r, n * sizeof(double)));
+    HIPCHK(move(host->dual_obj, v.p_dual_obj + r, n * sizeof(double)));
+    HIPCHK(move(host->status, v.p_status + r, n * sizeof(int32_t)));
+    HIPCHK(move(host->iters, v.p_iters + r, n * sizeof(int32_t)));
+    HIPCHK(move(host->primal, v.p_primal + r * d.n_primal, n * d.n_primal * sizeof(double)));
+    HIPCHK(move(host->dual, v.p_dual + r * d.n_dual, n * d.n_dual * sizeof(double)));
+    return HMPC_OK;
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "hmpc_device.h"
+#include "hmpc_host.h" // the entries at the end of this file: hmpc_handle, the staging table and its transfers
 
 struct ShiftArgs {
     int B, K;
@@ -559,4 +560,132 @@ __global__ void __launch_bounds__(1024) hmpc_shift_row_kernel(const DevProb p, c
         }
         own_c = own_n; own_n = own_nn; fix_c = fix_n; src_c = src_n; ub_c = ub_n;
     }
+}
+
+// ---- Host side: the launcher and the entries of include/hmpc.h ------------------------------------------------------------------
+// (shared with the fleet driver, which passes a row indirection)
+static int hmpc_launch_shift(hmpc_handle *h, const ShiftArgs &a, void *stream)
+{
+    const int B = a.B;
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    {   // rows staged in LDS by the memory pipeline (the second kernel above): one workgroup per CU, a row buffer per wave
+        const char *rows_env = getenv("HMPC_SHIFT_ROWS");   // (read per launch: the tests run both kernels in one process)
+        const bool off = rows_env && atoi(rows_env) == 0;
+        static const int cap = getenv("HMPC_SHIFT_ROW_WAVES") ? atoi(getenv("HMPC_SHIFT_ROW_WAVES")) : 0;   // (diagnostic)
+        const size_t fixed = hmpc_shift_row_fixed_doubles(h->dp), per = hmpc_shift_row_wave_doubles(h->dp), room = LDS_PER_CU / sizeof(double);
+        int waves = fixed < room ? (int)((room - fixed) / per) : 0;
+        if (waves > 16) waves = 16;
+        if (cap > 0 && cap < waves) waves = cap;
+        const DevProb &q = h->dp;
+        if (!off && h->shift_MT2 && waves >= 4 && q.n_dual >= 2 && q.nub >= 1 && q.nc >= 1 && q.ncL >= 1 && q.nq >= 1 && q.nr >= 1 && q.nx >= 1) {
+            const size_t lds = (fixed + (size_t)waves * per) * sizeof(double), need_tv = (size_t)a.K * hmpc_shift_tree_doubles(q);
+            HIPCHK(h->shift_tv.grow(need_tv, need_tv, (hipStream_t)stream)); // (with the number of trees: the stream's earlier launches still read the old block)
+            int grid = cus > 0 ? cus : 256;
+            const int need = (B + waves - 1) / waves;
+            if (grid > need) grid = need;
+            if (hipFuncSetAttribute((const void *)hmpc_shift_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) {
+                hipLaunchKernelGGL(hmpc_shift_tree_kernel, dim3(a.K), dim3(64), 0, (hipStream_t)stream, h->dp, a.K, a.x0, a.u0, h->shift_tv);
+                hipLaunchKernelGGL(hmpc_shift_row_kernel, dim3(grid), dim3(64 * waves), lds, (hipStream_t)stream, h->dp, a, (const double *)h->shift_tv, (const double2 *)h->shift_MT2);
+                HIPCHK(hipGetLastError());
+                return HMPC_OK;
+            }
+            (void)hipGetLastError();
+        }
+    }
+    // persistent workgroups: enough to fill the device, each wave walks leaves with stride grid * SHIFT_WAVES
+    const bool staged = hmpc_shift_lds_doubles(h->dp, true) * sizeof(double) <= 64 * 1024;
+    const size_t lds = hmpc_shift_lds_doubles(h->dp, staged) * sizeof(double);
+    int per_cu = (int)(LDS_PER_CU / (lds > 0 ? lds : 1));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) return fail(HMPC_ETOOBIG, "the shift's last-stage vectors exceed one CU's LDS");
+    int grid = (cus > 0 ? cus : 256) * per_cu;
+    const int need = (B + SHIFT_WAVES - 1) / SHIFT_WAVES;
+    if (grid > need) grid = need;
+    if (staged) {
+        if (lds > 48 * 1024)
+            (void)hipFuncSetAttribute((const void *)hmpc_shift_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(hmpc_shift_kernel<true>, dim3(grid), dim3(64 * SHIFT_WAVES), lds, (hipStream_t)stream, h->dp, a);
+    } else {
+        hipLaunchKernelGGL(hmpc_shift_kernel<false>, dim3(grid), dim3(64 * SHIFT_WAVES), lds, (hipStream_t)stream, h->dp, a);
+    }
+    HIPCHK(hipGetLastError());
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_set_shift_maps(hmpc_handle *h, const hmpc_shift_maps *m)
+{
+    g_err.clear();
+    if (!h || !m || !m->M_mu || !m->M_rho || !m->V) return fail(HMPC_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->device));
+    DevProb &p = h->dp;
+    // the retain rule of the shift kernel reads one binary per lane of a wavefront
+    if (p.nub > 64) return fail(HMPC_EINVAL, "the node shift supports at most 64 binaries per stage");
+    // a second call replaces the maps (the previous device copies are released)
+    h->shift_blocks.clear();
+    p.shift_Mmu = p.shift_Mrho = p.shift_V = h->shift_MT2 = nullptr;
+    // M_mu also in pairs of columns: [pair][row] -> (column 2k, column 2k + 1), an odd last column paired with zeros
+    const size_t ncL2 = ((size_t)p.ncL + 1) / 2;
+    std::vector<double> mt(2 * ncL2 * p.nc, 0.0);
+    for (int r = 0; r < p.nc; r++)
+        for (int k = 0; k < p.ncL; k++) mt[((size_t)(k / 2) * p.nc + r) * 2 + (k & 1)] = m->M_mu[(size_t)r * p.ncL + k];
+    auto vec = [](const double *a, size_t n) { return std::vector<double>(a, a + n); };
+    Uploader up{h->shift_blocks};
+    up(vec(m->M_mu, (size_t)p.nc * p.ncL), p.shift_Mmu);
+    up(vec(m->M_rho, (size_t)p.nq * p.nqT), p.shift_Mrho);
+    up(vec(m->V, (size_t)p.nub * p.nu), p.shift_V);
+    up(mt, h->shift_MT2);
+    return up.rc;
+}
+
+// what can be said about the arguments of a shift without the device (the maps apart: each entry asks for them in its own place)
+static int shift_arguments(const hmpc_handle *h, int32_t B, int32_t K, const void *const (&arrays)[13])
+{
+    if (!h) return fail(HMPC_EINVAL, "null handle");
+    if (B < 0 || K < 1) return fail(HMPC_EINVAL, "bad leaf or tree count");
+    if (B == 0) return HMPC_OK;
+    for (const void *a : arrays)
+        if (!a) return fail(HMPC_EINVAL, "null argument");
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_shift_batch_device(hmpc_handle *h, int32_t B, int32_t K, const int32_t *d_owner, const double *d_x0,
+                                       const double *d_u0, const double *d_e0, const int8_t *d_fix, const double *d_lb,
+                                       const double *d_dual, const double *d_dual_obj, int8_t *d_fix_out, double *d_lb_out,
+                                       double *d_dual_out, double *d_dual_obj_out, uint8_t *d_flags, void *stream)
+{
+    g_err.clear();
+    if (h && !h->dp.shift_Mmu) return fail(HMPC_EINVAL, "hmpc_set_shift_maps has not been called");
+    const int rc = shift_arguments(h, B, K, {d_owner, d_x0, d_u0, d_e0, d_fix, d_lb, d_dual, d_dual_obj, d_fix_out, d_lb_out, d_dual_out, d_dual_obj_out, d_flags});
+    if (rc) return rc;
+    if (B == 0) return HMPC_OK;
+    if (d_dual == d_dual_out || d_fix == d_fix_out) return fail(HMPC_EINVAL, "the shift is not in place");
+    HIPCHK(hipSetDevice(h->device));
+    ShiftArgs a{B, K, d_owner, d_x0, d_u0, d_e0, d_fix, d_lb, d_dual, d_dual_obj, nullptr, d_fix_out, d_lb_out, d_dual_out, d_dual_obj_out, d_flags};
+    return hmpc_launch_shift(h, a, stream);
+}
+
+// Its own device block (d_shift, exact fit) and no pinned mirror: one pageable copy per array up and down, on the null stream
+extern "C" int hmpc_shift_batch(hmpc_handle *h, int32_t B, int32_t K, const int32_t *owner, const double *x0, const double *u0,
+                                const double *e0, const int8_t *fix, const double *lb, const double *dual, const double *dual_obj,
+                                int8_t *fix_out, double *lb_out, double *dual_out, double *dual_obj_out, uint8_t *flags)
+{
+    g_err.clear();
+    int rc = shift_arguments(h, B, K, {owner, x0, u0, e0, fix, lb, dual, dual_obj, fix_out, lb_out, dual_out, dual_obj_out, flags});
+    if (rc) return rc;
+    if (B == 0) return HMPC_OK;
+    if (!h->dp.shift_Mmu) return fail(HMPC_EINVAL, "hmpc_set_shift_maps has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    const StageTable t = stage_shift(stage_dims(h), (size_t)B, (size_t)K, owner, x0, u0, e0, fix, lb, dual, dual_obj, fix_out, lb_out, dual_out, dual_obj_out, flags);
+    HIPCHK(h->d_shift.grow(t.total, t.total, nullptr));
+    char *base = h->d_shift;
+    if ((rc = stage_each_up(t, base, true))) return rc;
+    const ShiftArgs a{B, K, t.at<int32_t>(SH_OWNER, base), t.at<double>(SH_X0, base), t.at<double>(SH_U0, base), t.at<double>(SH_E0, base),
+                      t.at<int8_t>(SH_FIX, base), t.at<double>(SH_LB, base), t.at<double>(SH_DUAL, base), t.at<double>(SH_DOBJ, base), nullptr,
+                      t.at<int8_t>(SH_O_FIX, base), t.at<double>(SH_O_LB, base), t.at<double>(SH_O_DUAL, base), t.at<double>(SH_O_DOBJ, base),
+                      t.at<uint8_t>(SH_O_FLAGS, base)}; // (all thirteen are required: a pointer each, also where nub == 0 leaves a part empty)
+    if ((rc = hmpc_launch_shift(h, a, nullptr))) return rc;
+    if ((rc = stage_each_down(t, base, true))) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    return HMPC_OK;
 }
