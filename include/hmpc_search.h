@@ -97,6 +97,22 @@ int hmpc_search_results(hmpc_search *s, double *cost, double *u0, double *x1, in
 int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, int8_t *fix, double *lb, double *dual,
                        double *dual_obj, uint8_t *has_dual);
 
+/* The step that ended becomes the cover of the next one, on the device (the reference's construct_warm_start,
+ * controller.py:431-564, for all K trees): retain -> shift -> adopt, then the state of a fresh hmpc_search_begin.
+ * e0 (K x nx, host; NULL: zeros): the model error of the step.  x0_next (K x nx, host; NULL: x1 + e0 from the incumbent's row).
+ * cover, reopened (K each, host, nullable): leaves tree k carries over / how many of them carry no usable bound.
+ * Requires hmpc_set_shift_maps, a begun step and no staged round.
+ * A tree advances if and only if its state is exactly DONE | INCUMBENT; every other tree gets an empty cover (and, without
+ * x0_next, keeps its x0).  Of an advancing tree the alive nodes whose stage-0 binaries are free or those of the incumbent's
+ * input (rounded) are kept, in list order; kept leaf j of tree k becomes node j, with the shifted identifier, the shifted bound
+ * and row first[k] + j of the pool, whose rows 0 .. B - 1 are the shifted dual rows (B: all kept leaves; the next round's
+ * records begin at row B).  A leaf that carried no row shifts from a row of zeros and counts as reopened.
+ * A tree one of whose kept leaves the shift kernel dropped -- the two disagree on the retain rule -- begins the next step
+ * HMPC_SEARCH_FAILED.
+ * HMPC_EINVAL: a tree is still running (state 0).  HMPC_ETOOBIG: B > row_cap.  Either way nothing has changed.
+ * One readback (12 bytes) is the only synchronisation when cover and reopened are NULL. */
+int hmpc_search_advance(hmpc_search *s, const double *e0, const double *x0_next, int32_t *cover, int32_t *reopened, void *stream);
+
 /* Host copies, for a caller that solves the staged round elsewhere and for inspection (each synchronises; any array NULL).
  * get_batch: the staged round (B: its size) -- x0 (B x nx), fix (B x T*nub), the rows handed down, and the (tree, node) of
  *   every pick.

@@ -1,10 +1,11 @@
 // hmpc_search.h -- what one tree of a device-resident search does in a round (include/hmpc_search.h), item by item.
 //
 // Plain inline functions that compile for the device (hipcc) and for the host (g++), as hmpc_branch.h does: which nodes are
-// candidates and in which order they are picked, and what consuming ONE pick does to its tree.  Every decision about a record
-// is a function of hmpc_branch.h (branch_word, branch_child_lb, branch_child_warm; pos from branch_pos_*): nothing of it is
-// restated here.  The kernels (hmpc_search.hip) supply the workgroup argmin, the scan over the trees and the lane loops over
-// identifier rows; tests/host/search_driver.cpp walks the same functions serially under AddressSanitizer.
+// candidates and in which order they are picked, what consuming ONE pick does to its tree, and what the end of a step does to it
+// (hmpc_search_advance: which leaves it keeps, what the shift is given for them, what adoption makes of the tree).  Every decision
+// about a record is a function of hmpc_branch.h (branch_word, branch_child_lb, branch_child_warm; pos from branch_pos_*): nothing
+// of it is restated here.  The kernels (hmpc_search.hip) supply the workgroup argmin, the scan over the trees and the lane loops over
+// identifier rows; tests/host/search_driver.cpp and advance_driver.cpp walk the same functions serially under AddressSanitizer.
 //
 // Semantics: tree_select / tree_consume of hmpc_tree.h without speculation and dive (reference: branch_and_bound.py:462-489),
 // with the record's decision taken as hmpc_branch_batch takes it (`obj < cutoff`: a NaN objective prunes).
@@ -145,5 +146,96 @@ HMPC_HD int search_consume_pick(const BranchDims &d, const SearchState &s, const
 
 // entry j of the v-branch's identifier, f the parent's entry
 HMPC_HD int8_t search_child_fix(int8_t f, int j, int pos, int v) { return j == pos ? (int8_t)v : f; }
+
+// ---- advance: the step that ended becomes the cover of the next one (hmpc_search_advance) --------------------------------------
+// Per tree what tree_retain / fleet_stage_shift / tree_adopt_shifted of hmpc_tree.h do on the host, for slabs: which leaves a tree
+// carries over, what the shift is given for each of them, and what the shift's outputs make of the tree.  The shift itself is
+// hmpc_launch_shift (hmpc_shift.hip) between stage and adopt; its retain rule is search_retain_item.
+struct SearchShift {
+    int32_t *keep, *kept, *first;         // K x node_cap: a tree's kept nodes in list order; K: their number; K: its exclusive scan
+    int32_t *word;                        // [0] kept leaves of all trees  [1] a tree is still running  [2] they fit the pool
+    int32_t *owner, *src;                 // the staged leaves, tree by tree: tree, pool row its dual row is read from (row_cap: the zero row)
+    int8_t *fix;                          // x nfix
+    double *lb;
+    double *u0, *e0, *x0_next;            // K x nu (zeros: the tree does not advance), K x nx, K x nx
+    int8_t *fix_out;                      // what the shift returns for leaf b
+    double *lb_out;
+    uint8_t *flags;                       // bit 0: the shift kept it too, bit 1: reopened
+    int32_t *cover, *reopened;            // K each
+};
+
+// a tree advances if and only if its search ended with an incumbent and nothing else
+HMPC_HD bool search_advances(int32_t state) { return state == (HMPC_SEARCH_DONE | HMPC_SEARCH_INCUMBENT); }
+
+// retain rule (tree_retain; both shift kernels): entry q < nub of an identifier against the incumbent's q-th binary of stage 0
+HMPC_HD bool search_retain_item(int8_t f, double u) { return f < 0 || f == (int)rint(u); }
+
+// u0: the incumbent's inputs of stage 0 (primal + o_u)
+HMPC_HD bool search_retained(const BranchDims &d, const int8_t *fix, const double *u0)
+{
+    bool agree = true;
+    for (int q = 0; q < d.nub && agree; q++) agree = search_retain_item(fix[q], u0[d.nu - d.nub + q]);
+    return agree;
+}
+
+HMPC_HD const double *search_incumbent_u0(const BranchDims &d, const SearchState &s, const SearchTree &t)
+{
+    return s.p_primal + (size_t)*t.inc_row * d.n_primal + d.o_u;
+}
+
+// serial form of one tree's retain: its kept nodes in list order into keep (node_cap entries); returns their number
+HMPC_HD int search_retain_serial(const BranchDims &d, const SearchState &s, const SearchTree &t, int32_t *keep)
+{
+    if (!search_advances(*t.state)) return 0;
+    const double *u0 = search_incumbent_u0(d, s, t);
+    int cnt = 0;
+    for (int i = 0; i < *t.n; i++)
+        if (t.alive[i] && search_retained(d, t.fix + (size_t)i * d.nfix, u0)) keep[cnt++] = i;
+    return cnt;
+}
+
+// the pool row a staged leaf is shifted from: a node that carries none shifts from the zero row behind the pool
+HMPC_HD int32_t search_shift_src(int32_t row, int32_t row_cap) { return row >= 0 ? row : row_cap; }
+
+// everything of staged leaf b = node i of tree k but its identifier row
+HMPC_HD void search_stage_leaf(const SearchState &s, const SearchTree &t, const SearchShift &g, int k, int i, size_t b)
+{
+    g.owner[b] = k;
+    g.src[b] = search_shift_src(t.row[i], s.row_cap);
+    g.lb[b] = t.lb[i];
+}
+
+// entry e of tree k's rows for the shift and for the next step: the applied input (zeros where the tree does not advance) and
+// the next state (x1 + e0: ONE addition; a tree that does not advance keeps its state)
+HMPC_HD double search_stage_u0(const double *primal_u0, bool advances, int e) { return advances ? primal_u0[e] : 0.0; }
+HMPC_HD double search_stage_x0(const double *primal, int nx, bool advances, double x0, double e0, int e) { return advances ? primal[nx + e] + e0 : x0; }
+
+// whether staged leaf b counts as reopened: the shift says so, or it carried no dual row
+HMPC_HD bool search_leaf_reopened(const SearchState &s, const SearchShift &g, size_t b) { return (g.flags[b] & 2) != 0 || g.src[b] == s.row_cap; }
+
+// staged leaf b becomes node j of its tree (everything but the identifier row); returns whether the shift kept it too
+HMPC_HD bool search_adopt_leaf(const SearchTree &t, const SearchShift &g, int j, size_t b)
+{
+    t.lb[j] = g.lb_out[b];
+    t.row[j] = (int32_t)b; // (a reopened leaf carries its row too: it is solved again before anything reads it)
+    t.wrow[j] = -1;        // (the records of the step that ends here are not handed down across the shift)
+    t.alive[j] = 1;
+    return (g.flags[b] & 1) != 0;
+}
+
+// the scalars of tree k as hmpc_search_begin_kernel leaves them; agreed: the shift kept every leaf the retain rule kept
+HMPC_HD void search_adopt_scalars(const SearchState &s, const SearchTree &t, int k, int n, bool agreed)
+{
+    *t.n = n;
+    *t.ub = INFINITY;
+    *t.inc = -1;
+    *t.inc_row = -1;
+    *t.solves = 0;
+    *t.uncertified = 0;
+    *t.unc_lb = INFINITY;
+    *t.state = agreed ? 0 : HMPC_SEARCH_FAILED;
+    s.count[k] = 0;
+    s.offset[k] = 0;
+}
 
 #endif // HMPC_SEARCH_CORE_H

@@ -16,7 +16,8 @@
 //             (search_consume_pick: a COMPLETE pick lowers the cutoff of the next), all lanes compute pos and copy the two
 //             identifier rows of a branched node
 // and at the end of a step: results (one wavefront per tree: the incumbent's u0, x1 and identifier, the number of leaves) and
-// leaves (one wavefront per tree: its alive nodes in list order, 64 at a time by ballot, each copied with the rows it carries).
+// leaves (one wavefront per tree: its alive nodes in list order, 64 at a time by ballot, each copied with the rows it carries),
+// or, without leaving the device, advance: retain -> offsets -> stage -> the node shift (hmpc_launch_shift) -> adopt, further down.
 // Memory bound and small; nothing is staged in LDS but the four partial minima.  Plain C++ stores only: every store is a vector store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,6 +76,30 @@ __global__ void __launch_bounds__(SEARCH_SELECT_THREADS) hmpc_search_select_kern
     if (tid == 0) s.count[k] = cnt;
 }
 
+// Exclusive scan of v over the SEARCH_SCAN_CHUNK threads of the workgroup, in thread order; chunk: the sum over all of them.
+// totals: SEARCH_SCAN_CHUNK / 64 entries of LDS, free again when the call returns.
+static __device__ __forceinline__ int32_t search_chunk_scan(int32_t v, int32_t *totals, int lane, int wave, int32_t &chunk)
+{
+    int32_t incl = v; // inclusive scan within the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) totals[wave] = incl;
+    __syncthreads();
+    int32_t before = 0;
+    chunk = 0;
+#pragma unroll
+    for (int w = 0; w < SEARCH_SCAN_CHUNK / 64; w++) {
+        const int32_t tw = totals[w];
+        before += w < wave ? tw : 0;
+        chunk += tw;
+    }
+    __syncthreads(); // (the next call overwrites the totals)
+    return before + incl - v;
+}
+
 __global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_offsets_kernel(const BranchDims d, const SearchState s, const int row0, const int handdown)
 {
     __shared__ int32_t totals[SEARCH_SCAN_CHUNK / 64];
@@ -90,24 +115,10 @@ __global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_offsets_kernel(
             const int32_t *wrow = s.wrow + (size_t)k * s.node_cap;
             for (int j = 0; j < v; j++) warm |= search_warm_index(wrow[s.picks[(size_t)k * SEARCH_MAX_WIDTH + j]], handdown) >= 0;
         }
-        int32_t incl = v; // inclusive scan within the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t up = __shfl_up(incl, o);
-            if (lane >= o) incl += up;
-        }
-        if (lane == 63) totals[wave] = incl;
-        __syncthreads();
-        int32_t before = 0, chunk = 0;
-#pragma unroll
-        for (int w = 0; w < SEARCH_SCAN_CHUNK / 64; w++) {
-            const int32_t tw = totals[w];
-            before += w < wave ? tw : 0;
-            chunk += tw;
-        }
-        if (k < s.K) s.offset[k] = carry + before + incl - v;
+        int32_t chunk;
+        const int32_t before = search_chunk_scan(v, totals, lane, wave, chunk);
+        if (k < s.K) s.offset[k] = carry + before;
         carry += chunk; // (at most K SEARCH_MAX_WIDTH, which hmpc_search_create holds below 2^31)
-        __syncthreads(); // (the next chunk overwrites the totals)
     }
     bad = __syncthreads_or(bad);
     warm = __syncthreads_or(warm);
@@ -278,6 +289,111 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_begin_kernel(co
     }
 }
 
+// ---- advance: retain -> offsets -> stage -> [hmpc_launch_shift] -> adopt (arithmetic: hmpc_search.h) ---------------------------
+// retain   one wavefront per tree: its nodes 64 at a time, each lane tests its own node's stage-0 entries against the incumbent's
+//          input; the kept nodes go into the tree's index list in list order (ballot, rank = kept lanes below), with their number
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_retain_kernel(const BranchDims d, const SearchState s, const SearchShift g)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
+        const SearchTree t = search_tree(s, d.nfix, k);
+        int cnt = 0;
+        if (search_advances(*t.state)) { // (the same in every lane)
+            const int n = *t.n;
+            const double *u0 = search_incumbent_u0(d, s, t);
+            int32_t *keep = g.keep + (size_t)k * s.node_cap;
+            for (int base = 0; base < n; base += 64) {
+                const int mine = base + lane;
+                const bool kept = mine < n && t.alive[mine] != 0 && search_retained(d, t.fix + (size_t)mine * d.nfix, u0);
+                const unsigned long long m = __ballot(kept);
+                if (kept) keep[cnt + __popcll(m & ((1ull << lane) - 1))] = mine; // < n <= node_cap
+                cnt += __popcll(m);
+            }
+        }
+        if (lane == 0) g.kept[k] = cnt;
+    }
+}
+
+// offsets  ONE workgroup: where every tree's kept leaves begin (the scan of the rounds' offsets kernel), and the word the host reads
+__global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_advance_offsets_kernel(const SearchState s, const SearchShift g)
+{
+    __shared__ int32_t totals[SEARCH_SCAN_CHUNK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t carry = 0;
+    int running = 0;
+    for (int base = 0; base < s.K; base += SEARCH_SCAN_CHUNK) {
+        const int k = base + tid;
+        int32_t v = 0;
+        if (k < s.K) {
+            v = g.kept[k];
+            running |= search_running(s.state[k]);
+        }
+        int32_t chunk;
+        const int32_t before = search_chunk_scan(v, totals, lane, wave, chunk);
+        if (k < s.K) g.first[k] = carry + before;
+        carry += chunk; // (at most K node_cap, which hmpc_search_create holds below 2^31)
+    }
+    running = __syncthreads_or(running);
+    if (tid == 0) {
+        g.word[0] = carry;
+        g.word[1] = running != 0;
+        g.word[2] = carry <= s.row_cap;
+    }
+}
+
+// stage    one wavefront per tree: what the shift reads -- per kept leaf its tree, the row it carries, its bound and its identifier,
+//          per tree the applied input and the next state (given != 0: the caller's, already in place)
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_advance_stage_kernel(const BranchDims d, const SearchState s, const SearchShift g, const int given)
+{
+    if (g.word[1] || !g.word[2]) return; // refused: a tree is running, or the leaves do not fit the pool
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
+        const SearchTree t = search_tree(s, d.nfix, k);
+        const bool adv = search_advances(*t.state);
+        const double *w = adv ? s.p_primal + (size_t)*t.inc_row * d.n_primal : nullptr;
+        for (int e = lane; e < d.nu; e += 64) g.u0[(size_t)k * d.nu + e] = search_stage_u0(adv ? w + d.o_u : nullptr, adv, e);
+        if (!given)
+            for (int e = lane; e < d.nx; e += 64)
+                g.x0_next[(size_t)k * d.nx + e] = search_stage_x0(w, d.nx, adv, s.x0[(size_t)k * d.nx + e], g.e0[(size_t)k * d.nx + e], e);
+        const int cnt = g.kept[k];
+        const size_t first = (size_t)g.first[k]; // first + cnt <= B <= row_cap
+        const int32_t *keep = g.keep + (size_t)k * s.node_cap;
+        for (int j = lane; j < cnt; j += 64) search_stage_leaf(s, t, g, k, keep[j], first + j);
+        for (int j = 0; j < cnt; j++) {
+            const int8_t *fix = t.fix + (size_t)keep[j] * d.nfix;
+            for (int e = lane; e < d.nfix; e += 64) g.fix[(first + j) * d.nfix + e] = fix[e];
+        }
+    }
+}
+
+// adopt    one wavefront per tree: the shifted leaves are the tree (it reads the staging and the shift's outputs only, never the
+//          slab it overwrites); cover and reopened by shuffles; a kept leaf the shift dropped stops the tree
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_adopt_kernel(const BranchDims d, const SearchState s, const SearchShift g)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
+        const SearchTree t = search_tree(s, d.nfix, k);
+        const int cnt = g.kept[k]; // <= the tree's nodes <= node_cap
+        const size_t first = (size_t)g.first[k];
+        int dropped = 0, reop = 0;
+        for (int j = lane; j < cnt; j += 64) {
+            dropped |= !search_adopt_leaf(t, g, j, first + j);
+            reop += search_leaf_reopened(s, g, first + j);
+        }
+        for (int j = 0; j < cnt; j++)
+            for (int e = lane; e < d.nfix; e += 64) t.fix[(size_t)j * d.nfix + e] = g.fix_out[(first + j) * d.nfix + e];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) reop += __shfl_xor(reop, o);
+        dropped = __any(dropped);
+        for (int e = lane; e < d.nx; e += 64) s.x0[(size_t)k * d.nx + e] = g.x0_next[(size_t)k * d.nx + e];
+        if (lane == 0) {
+            search_adopt_scalars(s, t, k, cnt, !dropped);
+            g.cover[k] = cnt;
+            g.reopened[k] = reop;
+        }
+    }
+}
+
 // ---- Host side: the entries of include/hmpc_search.h (arithmetic: hmpc_search.h) -----------------------------------------------
 struct hmpc_search {
     hmpc_handle *h = nullptr;
@@ -289,6 +405,14 @@ struct hmpc_search {
     DevBuf<uint8_t> alive;
     DevBuf<char> tmp;      // begin's compact trees, the outputs of results and leaves (hmpc_stage.h; exact fit, one blocking copy per array)
     PinBuf<int32_t> h_word;
+    // hmpc_search_advance, allocated at its first call: the staging of SearchShift, the second dual pool, pinned mirrors
+    SearchShift a{};
+    DevBuf<int32_t> a_idx;
+    DevBuf<int8_t> a_fix;
+    DevBuf<uint8_t> a_flags;
+    DevBuf<double> a_val, q_dual, q_dual_obj; // q_*: the pool the next shift writes (the two swap with every advance)
+    PinBuf<double> a_hval;                    // e0 | x0_next on their way up
+    PinBuf<int32_t> a_hidx;                   // word (4) | cover | reopened on their way down
     int32_t row0 = 0;      // first pool row of the staged (or next) round
     int32_t staged = 0;    // size of the staged round, 0: none
     bool begun = false;
@@ -324,11 +448,13 @@ extern "C" int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, i
     HIPCHK(s->td.alloc(2 * k));
     HIPCHK(s->x0.alloc(k * d.nx));
     HIPCHK(s->p_obj.alloc(rows));
-    HIPCHK(s->p_dual_obj.alloc(rows));
+    HIPCHK(s->p_dual_obj.alloc(rows + 1)); // (one row of zeros behind the pool, for the shift of a leaf that carries none: hmpc_search_advance)
     HIPCHK(s->p_status.alloc(rows));
     HIPCHK(s->p_iters.alloc(rows));
     HIPCHK(s->p_primal.alloc(rows * d.n_primal));
-    HIPCHK(s->p_dual.alloc(rows * d.n_dual));
+    HIPCHK(s->p_dual.alloc((rows + 1) * d.n_dual));
+    HIPCHK(hipMemset(s->p_dual + rows * d.n_dual, 0, d.n_dual * sizeof(double)));
+    HIPCHK(hipMemset(s->p_dual_obj + rows, 0, sizeof(double)));
     HIPCHK(s->picks.alloc(k * SEARCH_MAX_WIDTH));
     HIPCHK(s->count.alloc(k));
     HIPCHK(s->offset.alloc(k));
@@ -546,6 +672,96 @@ extern "C" int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, in
     hipLaunchKernelGGL(hmpc_search_leaves_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, nullptr, d, s->v, o);
     HIPCHK(hipGetLastError());
     return stage_each_down(t, base, false);
+}
+
+// The staging of an advance and the second dual pool (callers that never advance pay nothing).
+static int search_advance_setup(hmpc_search *s, hipStream_t st)
+{
+    if (s->a.keep) return HMPC_OK;
+    const BranchDims &d = s->d;
+    const size_t K = (size_t)s->v.K, nodes = K * s->v.node_cap, rows = (size_t)s->v.row_cap;
+    const size_t cap = std::min(nodes, rows); // staged leaves at most: more are refused at the readback
+    HIPCHK(s->a_idx.alloc(nodes + 4 * K + 4 + 2 * cap));
+    HIPCHK(s->a_fix.alloc(2 * cap * d.nfix));
+    HIPCHK(s->a_flags.alloc(cap));
+    HIPCHK(s->a_val.alloc(2 * cap + K * d.nu + 2 * K * d.nx));
+    HIPCHK(s->q_dual.alloc((rows + 1) * d.n_dual));
+    HIPCHK(s->q_dual_obj.alloc(rows + 1));
+    HIPCHK(s->a_hval.alloc(2 * K * d.nx));
+    HIPCHK(s->a_hidx.alloc(4 + 2 * K));
+    HIPCHK(hipMemsetAsync(s->q_dual + rows * d.n_dual, 0, d.n_dual * sizeof(double), st)); // (its row of zeros, as hmpc_search_create)
+    HIPCHK(hipMemsetAsync(s->q_dual_obj + rows, 0, sizeof(double), st));
+    int32_t *i = s->a_idx;
+    int8_t *f = s->a_fix;
+    double *v = s->a_val;
+    SearchShift &a = s->a;
+    a.kept = i; a.first = i + K; a.cover = i + 2 * K; a.reopened = i + 3 * K; a.word = i + 4 * K;
+    a.owner = i + 4 * K + 4; a.src = a.owner + cap;
+    a.fix = f; a.fix_out = f + cap * d.nfix;
+    a.lb = v; a.lb_out = v + cap; a.u0 = v + 2 * cap; a.e0 = a.u0 + K * d.nu; a.x0_next = a.e0 + K * d.nx;
+    a.flags = s->a_flags;
+    a.keep = a.src + cap; // (last: it says that all of this is in place)
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const double *x0_next, int32_t *cover, int32_t *reopened, void *stream)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
+    if (s->staged > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    if (!s->h->dp.shift_Mmu) return fail(HMPC_EINVAL, "search: hmpc_set_shift_maps has not been called");
+    HIPCHK(hipSetDevice(s->h->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_advance_setup(s, st);
+    if (rc) return rc;
+    const BranchDims &d = s->d;
+    const SearchShift &a = s->a;
+    const size_t K = (size_t)s->v.K, state = K * d.nx;
+    // e0 and x0_next through the pinned block (the readback below is behind both copies: the block is free again when this returns)
+    double *up = s->a_hval;
+    if (e0) std::copy(e0, e0 + state, up);
+    else std::fill(up, up + state, 0.0);
+    HIPCHK(hipMemcpyAsync(a.e0, up, state * sizeof(double), hipMemcpyHostToDevice, st));
+    if (x0_next) {
+        std::copy(x0_next, x0_next + state, up + state);
+        HIPCHK(hipMemcpyAsync(a.x0_next, up + state, state * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    const dim3 trees = search_grid((long long)K), waves(64 * SEARCH_WAVES);
+    hipLaunchKernelGGL(hmpc_search_retain_kernel, trees, waves, 0, st, d, s->v, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_advance_offsets_kernel, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->v, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_advance_stage_kernel, trees, waves, 0, st, d, s->v, a, (int)(x0_next != nullptr));
+    HIPCHK(hipGetLastError());
+    int32_t *down = s->a_hidx;
+    HIPCHK(hipMemcpyAsync(down, a.word, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // the one synchronisation of a step: how many leaves the shift is launched for
+    const int32_t B = down[0];
+    if (B < 0 || (long long)B > (long long)K * s->v.node_cap) return fail(HMPC_EDEVICE, "search: the device returned a number of kept leaves outside [0, K node_cap]");
+    if (down[1]) return fail(HMPC_EINVAL, "search: a tree is still running (its state is 0): the step has not ended");
+    if (!down[2]) return fail(HMPC_ETOOBIG, "search: the kept leaves do not fit the pool (row_cap)");
+    if (B > 0) {
+        const ShiftArgs g{B, (int)K, a.owner, s->v.x0, a.u0, a.e0, a.fix, a.lb, s->v.p_dual, s->v.p_dual_obj, a.src,
+                          a.fix_out, a.lb_out, s->q_dual, s->q_dual_obj, a.flags};
+        if ((rc = hmpc_launch_shift(s->h, g, st))) return rc;
+    }
+    hipLaunchKernelGGL(hmpc_search_adopt_kernel, trees, waves, 0, st, d, s->v, a);
+    HIPCHK(hipGetLastError());
+    // the pools swap: rows 0 .. B - 1 of the next step's pool are the shifted leaves'
+    std::swap(s->p_dual, s->q_dual);
+    std::swap(s->p_dual_obj, s->q_dual_obj);
+    s->v.p_dual = s->p_dual;
+    s->v.p_dual_obj = s->p_dual_obj;
+    s->row0 = B;
+    s->staged = 0;
+    if (cover || reopened) {
+        HIPCHK(hipMemcpyAsync(down + 4, a.cover, 2 * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (cover) std::copy(down + 4, down + 4 + K, cover);
+        if (reopened) std::copy(down + 4 + K, down + 4 + 2 * K, reopened);
+    }
+    return HMPC_OK;
 }
 
 // Host copies of the staged round, of one tree and of pool rows: for a caller that solves elsewhere, and for inspection.

@@ -176,6 +176,27 @@ class DeviceSearch(object):
             out.append(NodeArrays(f['fix'][m], f['lb'][m], f['dual'][m], f['dual_obj'][m], f['has_dual'][m]))
         return out
 
+    def advance(self, errors=None, x0_next=None, stats=True, stream=None):
+        """The step that ended becomes the cover of the next one without leaving the device (``hmpc_search_advance``): retain ->
+        shift -> adopt for all K trees, then the state of a fresh ``begin``.  errors (K, nx): the model errors of the step (None:
+        zeros); x0_next (K, nx): the next states (None: x1 + error of every tree that advances).  Needs the shift's maps
+        (``BatchedMPC(controller)`` or ``qp.set_shift_maps``).  Returns dict cover, reopened (K each) -- or, with ``stats=False``,
+        None and one synchronisation less.  Raises ``SearchTooBig``, with nothing changed, when the kept leaves outnumber the pool."""
+        def state(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+            if a.shape != (self.K, self.nx):
+                raise ValueError('%s must have shape (%d, %d).' % (name, self.K, self.nx))
+            return a
+        e0, xn = state(errors, 'errors'), state(x0_next, 'x0_next')
+        out = dict(cover=np.empty(self.K, dtype=np.int32), reopened=np.empty(self.K, dtype=np.int32)) if stats else None
+        self._check(self.qp.lib.hmpc_search_advance(self._s, None if e0 is None else e0.ctypes.data, None if xn is None else xn.ctypes.data,
+                                                    out['cover'].ctypes.data if stats else None, out['reopened'].ctypes.data if stats else None,
+                                                    ctypes.c_void_p(stream)))
+        self._B = 0
+        return out
+
     def tree(self, k):
         """Tree k as it stands (for inspection): scalars and the whole slab, node_cap entries each."""
         nc = self.node_cap
@@ -214,16 +235,51 @@ class DeviceSearch(object):
             out.append(d)
         return out
 
-    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True):
-        """K closed loops from the same x0 under prescribed model errors (K, n_steps, nx), as ``FleetMPC.closed_loop``: per step
-        ``run``, then the leaves go through the backend's node shift (``hmpc_shift_batch``) and become the covers of ``begin``.
+    def _closed_loop_resident(self, x0s, n_steps, errors, frontier_width, tol, handdown):
+        """``closed_loop`` with the trees, the pool and the step boundary on the device: ``begin`` once, then per step ``run`` ->
+        ``results`` (K small rows) -> ``advance``.  A tree without an incumbent gets an empty cover and stays empty."""
+        K = self.K
+        stats = dict(nodes_ws=np.zeros((K, n_steps), np.int64), len_ws=np.zeros((K, n_steps), np.int64), reopened=np.zeros((K, n_steps), np.int64),
+                     costs=np.full((K, n_steps), np.nan))
+        alive = np.ones(K, dtype=bool)
+        tic = perf_counter()
+        steps = 0
+        self.begin(x0s)
+        for t in range(n_steps):
+            if not alive.any():
+                break
+            self.run(frontier_width, tol, handdown)
+            r = self.results()
+            bad = r['state'] & (SEARCH_STATES['failed'] | SEARCH_STATES['overflow'])
+            if np.any(bad & SEARCH_STATES['failed']):
+                raise RuntimeError('QP solver did not converge on a node of %d searches' % int(((bad & SEARCH_STATES['failed']) != 0).sum()))
+            if np.any(bad):
+                raise RuntimeError('%d trees outgrew node_cap = %d' % (int((bad != 0).sum()), self.node_cap))
+            stats['nodes_ws'][alive, t] = r['solves'][alive]
+            alive &= np.isfinite(r['cost'])
+            if not alive.any():
+                break
+            a = self.advance(errors[:, t])
+            stats['len_ws'][alive, t], stats['reopened'][alive, t], stats['costs'][alive, t] = a['cover'][alive], a['reopened'][alive], r['cost'][alive]
+            steps += int(alive.sum())
+        stats.update(steps=steps, wall=perf_counter() - tic)
+        return stats
+
+    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True, resident=False):
+        """K closed loops from the same x0 (or from K states, (K, nx)) under prescribed model errors (K, n_steps, nx), as
+        ``FleetMPC.closed_loop``: per step ``run``, then the leaves go through the backend's node shift (``hmpc_shift_batch``) and
+        become the covers of ``begin``.  ``resident=True``: the same walk with the step boundary on the device (``advance``) -- no
+        leaf, identifier or dual row crosses the bus.
         A loop whose MIQP is infeasible ends (its tree stays empty).  Returns dict of arrays (K, n_steps): nodes_ws, len_ws,
         reopened, costs (NaN where a loop has ended), steps, wall."""
         from .batched import BatchedMPC
         bm = BatchedMPC(self.c)                                 # (uploads the shift's maps)
         K = self.K
         errors = np.asarray(errors, dtype=np.float64)
-        xs = np.repeat(np.asarray(x0, dtype=np.float64)[None], K, axis=0)
+        xs = np.asarray(x0, dtype=np.float64)
+        xs = np.repeat(xs[None], K, axis=0) if xs.ndim == 1 else xs.copy()
+        if resident:
+            return self._closed_loop_resident(xs, n_steps, errors, frontier_width, tol, handdown)
         ws = None
         alive = np.ones(K, dtype=bool)
         nothing = NodeArrays(np.zeros((0, self.nfix), np.int8), np.zeros(0), np.zeros((0, self.n_dual)), np.zeros(0), np.zeros(0, bool))
