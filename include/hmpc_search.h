@@ -5,9 +5,9 @@
  * around those calls: which nodes of a tree go next, the incumbent, the tree itself (the reference's loop,
  * warm_start_hmpc/branch_and_bound.py:462-489; here tree_select / tree_consume of csrc/hmpc_tree.h and _Tree of
  * warm_start_hmpc_amd/batched.py, both on the host).  An hmpc_search keeps K independent trees in HBM and advances them in
- * lockstep, one QP launch per round; the host reads back one small word per round, the size of the next launch.
+ * lockstep, at most one QP launch per round; the host reads back one small word per round, the size of the next launch.
  *
- * Per tree the semantics are tree_select + tree_consume without speculation and without dive prediction:
+ * Per tree the semantics are tree_select + tree_consume without dive prediction and -- at the default depth 0 -- without speculation:
  *   select   candidates are the nodes with alive && lb < ub - tol; the `width` smallest by (lb, index) are picked, in that
  *            order (first wins ties; +inf bounds are never picked).  A tree without candidates gets HMPC_SEARCH_DONE, and
  *            HMPC_SEARCH_INCUMBENT with it if it has an incumbent.  Only trees whose state word is 0 take part.
@@ -25,6 +25,34 @@
  * index order; one pool of row_cap record rows in the layout of hmpc_result holds every solved node; a round's records are
  * rows row0 .. row0 + B - 1, and row0 advances by B with every consumed round.
  * The search uses the handle's workspaces through the solve call: at most ONE launch per handle may be in flight.
+ *
+ * Speculation (hmpc_search_set_speculation, depth s in 0 .. 4, default 0: everything above, bit for bit) is tree_expand of
+ * csrc/hmpc_tree.h without dive prediction: a launch of a few nodes costs a node's latency whatever it carries, so every picked
+ * node that has to be launched rides with ALL its descendants through its next s free binaries; their records wait in the pool,
+ * and a later pick of such a descendant is consumed from its waiting record without a launch.
+ * With S(L) = 2^(L+1) - 1 and pos(i) = the number of leading entries of node i's identifier up to its last fixed one, every node
+ * carries two more fields: srow, the pool row of its own waiting record or -1, and sleft, the levels of waiting descendants below
+ * that record.  begin, advance and a branch without waiting descendants set them to -1 and 0.
+ *   select   picks exactly as above -- speculation never changes which nodes a round picks.  A pick with srow[i] >= 0 emits no
+ *            row.  Any other pick emits a block of S(L) rows, L = min(s, T nub - pos(i)), in PRE-ORDER: row r is the node, row
+ *            r + 1 opens the 0-child's block of S(L-1) rows, row r + 1 + S(L-1) the 1-child's; row r + q carries the node's
+ *            identifier with the binaries at pos, pos + 1, ... set along the path that pre-order index q names.  Blocks lie tree
+ *            by tree and in pick order within a tree; B is the number of emitted rows, and row0 + B > row_cap is HMPC_ETOOBIG
+ *            with nothing changed.  Of the staged round a block's first row receives the row handed down to its node and carries
+ *            (tree, node); the descendants receive -1 (their parent rides in the same launch) and carry (tree, -1).
+ *   consume  a pick with srow[i] >= 0 uses r = srow[i], L = sleft[i]; a launched pick its block's first row and the L of select.
+ *            Then everything above happens with (i, r), the refusals included (a refused pick writes nothing, the two fields
+ *            neither), and: srow[i] = -1; child v of a BRANCHED node gets srow = r + 1 + v S(L-1), sleft = L - 1 if L > 0, else
+ *            -1 and 0.  The children still hand row r down: it is used once a child without waiting descendants has children of
+ *            its own to launch.  A waiting record with status > HMPC_INFEASIBLE fails its tree WHEN IT IS CONSUMED, never
+ *            before; waiting records that are never consumed change nothing, and begin and advance drop them.
+ * With s > 0 a round may have picks and no launch (every pick's record waits): B == 0 no longer says that every tree has
+ * stopped -- the number of picks P does (hmpc_search_staged), and it comes back in the round's one readback.
+ * The invariant: with hand-down off a record is a function of (x0, identifier) alone, so for any s every round's picks and every
+ * tree after every round equal those at s = 0 in every field but pool row numbers (row, wrow, inc_row) and srow / sleft; the
+ * records those row numbers point at are bit-equal; only the number of QP launches falls.  With hand-down ON this does not hold
+ * bit for bit: speculated descendants are solved cold, where at s = 0 they would have received their parent's record.
+ * A step needs up to S(s) pool rows per launched pick instead of one.
  */
 #ifndef HMPC_SEARCH_H
 #define HMPC_SEARCH_H
@@ -59,7 +87,7 @@ int hmpc_search_begin(hmpc_search *s, const double *x0, const int32_t *count, co
 
 /* One round in two halves, for callers that solve elsewhere and for the tests.
  * select stages the round and returns its size in *B: the one synchronisation of a round.  width in 1 .. 64.
- * B = 0: every tree has stopped.
+ * B = 0: every tree has stopped (at speculation depth 0; else see hmpc_search_staged).
  * row0 + B > row_cap: HMPC_ETOOBIG with nothing changed. */
 int hmpc_search_select(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t *B, void *stream);
 
@@ -74,11 +102,13 @@ int hmpc_search_batch(const hmpc_search *s, const double **d_x0, const int8_t **
  * obj, status, iters required, the other members are copied where given. */
 int hmpc_search_put_records(hmpc_search *s, int32_t B, const hmpc_result *host_records);
 
-/* Consumes the staged round.  Asynchronous on `stream`.  HMPC_EINVAL without a staged round. */
+/* Consumes the staged round.  Asynchronous on `stream`.  HMPC_EINVAL without a staged round (one without a pick). */
 int hmpc_search_consume(hmpc_search *s, double tol, void *stream);
 
-/* select -> hmpc_solve_batch_device -> consume until B == 0 or max_rounds (<= 0: none).  rounds, launched (nullable): QP
- * launches and nodes of this call.  The states of the trees say how each of them ended (hmpc_search_results). */
+/* select -> hmpc_solve_batch_device -> consume until no tree has a pick or max_rounds (<= 0: none).  rounds, launched
+ * (nullable): rounds and nodes of this call; at speculation depth 0 every round is one QP launch, else a round whose picks all
+ * have waiting records skips the solve and still consumes (hmpc_search_counters tells the two apart).  One synchronisation per
+ * round either way.  The states of the trees say how each of them ended (hmpc_search_results). */
 int hmpc_search_run(hmpc_search *s, int32_t width, double tol, int32_t handdown, int32_t max_rounds, void *stream,
                     int32_t *rounds, int64_t *launched);
 
@@ -123,6 +153,22 @@ int hmpc_search_get_batch(hmpc_search *s, int32_t B, double *x0, int8_t *fix, in
 int hmpc_search_tree(hmpc_search *s, int32_t k, int32_t *scalars6, double *bounds2, int8_t *fix, double *lb, int32_t *row,
                      int32_t *wrow, uint8_t *alive);
 int hmpc_search_rows(hmpc_search *s, int32_t first, int32_t count, const hmpc_result *host, int32_t write);
+
+/* Speculation depth of the rounds to come (see the top of this file), 0 .. 4; a new search has 0.  Regrows the staging of a
+ * round to min(K 64 S(depth), row_cap) rows, so that select never allocates.  HMPC_EINVAL: depth outside 0 .. 4 (checked first,
+ * without touching the GPU), a staged round, K 64 S(depth) beyond int32.  Waiting records of an earlier depth stay valid. */
+int hmpc_search_set_speculation(hmpc_search *s, int32_t depth);
+
+/* The staged round as the host knows it from select's readback, without a synchronisation: its picks (0: none is staged, the
+ * search has stopped) and its rows B.  Either pointer may be NULL. */
+int hmpc_search_staged(const hmpc_search *s, int32_t *picks, int32_t *B);
+
+/* out[4], all since hmpc_search_begin: rounds consumed, QP launches among them (rounds with B > 0), rows launched (the sum of B),
+ * picks whose record was waiting when their round was staged. */
+int hmpc_search_counters(const hmpc_search *s, int64_t *out);
+
+/* srow and sleft of tree k's slab, node_cap entries each (synchronises; either array NULL). */
+int hmpc_search_tree_waiting(hmpc_search *s, int32_t k, int32_t *srow, int32_t *sleft);
 
 #ifdef __cplusplus
 }

@@ -7,8 +7,10 @@
 // of it is restated here.  The kernels (hmpc_search.hip) supply the workgroup argmin, the scan over the trees and the lane loops over
 // identifier rows; tests/host/search_driver.cpp and advance_driver.cpp walk the same functions serially under AddressSanitizer.
 //
-// Semantics: tree_select / tree_consume of hmpc_tree.h without speculation and dive (reference: branch_and_bound.py:462-489),
-// with the record's decision taken as hmpc_branch_batch takes it (`obj < cutoff`: a NaN objective prunes).
+// Semantics: tree_select / tree_consume of hmpc_tree.h without dive (reference: branch_and_bound.py:462-489), with the record's
+// decision taken as hmpc_branch_batch takes it (`obj < cutoff`: a NaN objective prunes).  Speculation (tree_expand, dive = false)
+// is the block arithmetic further down: a launched pick rides with its descendants through its next binaries, in pre-order, and a
+// node knows the pool row of its own waiting record (srow) and how many levels of waiting descendants lie below it (sleft).
 #ifndef HMPC_SEARCH_CORE_H
 #define HMPC_SEARCH_CORE_H
 
@@ -30,10 +32,14 @@ struct SearchState {
     int32_t *p_status, *p_iters;
     double *p_primal, *p_dual;
     int32_t *picks, *count, *offset;      // the staged round: K x SEARCH_MAX_WIDTH nodes in selection order, K, K (exclusive scan of count)
-    int32_t *word;                        // [0] B  [1] a tree has stopped FAILED / OVERFLOW  [2] a node receives a record  [3] the round fits the pool
+    int32_t *word;                        // [0] B  [1] a tree has stopped FAILED / OVERFLOW  [2] a node receives a record  [3] the round fits the pool  [4] picks  [5] picks whose record waits
     int8_t *b_fix;                        // the batch: B x nfix
     double *b_x0;                         // B x nx
     int32_t *b_warm, *b_tree, *b_node;    // B each
+    // speculation (new members at the end: a state initialised without them has none -- srow == nullptr: no waiting records, depth 0)
+    int32_t *srow, *sleft;                // K node_cap: pool row of the node's own waiting record or -1 / levels of waiting descendants below it
+    int32_t *plev, *pfirst;               // the staged round, K x SEARCH_MAX_WIDTH: levels of a launched pick's block (-1: its record waits) / first row of the block within its tree's rows
+    int spec;                             // speculation depth, 0 .. SEARCH_MAX_SPEC
 };
 
 struct SearchTree { // one tree of it
@@ -43,13 +49,14 @@ struct SearchTree { // one tree of it
     uint8_t *alive;
     int32_t *n, *inc, *inc_row, *solves, *uncertified, *state;
     double *ub, *unc_lb;
+    int32_t *srow, *sleft; // (null without speculation)
 };
 
 HMPC_HD SearchTree search_tree(const SearchState &s, int nfix, int k)
 {
     const size_t o = (size_t)k * s.node_cap;
     return SearchTree{s.fix + o * nfix, s.lb + o, s.row + o, s.wrow + o, s.alive + o, s.n + k, s.inc + k, s.inc_row + k, s.solves + k,
-                      s.uncertified + k, s.state + k, s.ub + k, s.unc_lb + k};
+                      s.uncertified + k, s.state + k, s.ub + k, s.unc_lb + k, s.srow ? s.srow + o : nullptr, s.srow ? s.sleft + o : nullptr};
 }
 
 // ---- select --------------------------------------------------------------------------------------------------------------------
@@ -147,6 +154,77 @@ HMPC_HD int search_consume_pick(const BranchDims &d, const SearchState &s, const
 // entry j of the v-branch's identifier, f the parent's entry
 HMPC_HD int8_t search_child_fix(int8_t f, int j, int pos, int v) { return j == pos ? (int8_t)v : f; }
 
+// ---- speculation: a launched pick rides with its descendants through its next binaries -----------------------------------------
+// A block of L levels is the node and all its descendants through its next L free binaries, S(L) = 2^(L+1) - 1 rows in pre-order:
+// row 0 the node, row 1 opens the 0-child's block of S(L-1) rows, row 1 + S(L-1) the 1-child's.  With hand-down off a record is a
+// function of (x0, identifier) alone, so what rides along never changes a search, only the number of its launches; with hand-down
+// on the descendants are solved cold (their parent rides in the same launch, as in tree_expand) and the equality is not bit for bit.
+#define SEARCH_MAX_SPEC 4 // deepest speculation: blocks of at most S(4) = 31 rows
+
+HMPC_HD int search_block_rows(int L) { return (2 << L) - 1; }
+
+// levels of the block of a node whose identifier is fixed through pos: its free binaries bound the depth
+HMPC_HD int search_block_levels(int spec, int nfix, int pos) { return spec < nfix - pos ? spec : nfix - pos; }
+
+// the block of a pick: -1 where its record waits (the pick emits no row)
+HMPC_HD int search_pick_levels(int32_t srow, int spec, int nfix, int pos) { return srow >= 0 ? -1 : search_block_levels(spec, nfix, pos); }
+HMPC_HD int search_pick_rows(int lev) { return lev < 0 ? 0 : search_block_rows(lev); }
+
+// Row q of a block of L levels: returns its depth m below the node; bit j < m of *bits is the value of binary pos + j on the path.
+HMPC_HD int search_block_path(int L, int q, int *bits)
+{
+    int m = 0, b = 0;
+    while (q > 0) { // row 0 of the block that is left is the node on the path; q - 1 counts into the 0-child's block, then the 1-child's
+        L--;
+        q--;
+        const int half = search_block_rows(L);
+        const int v = q >= half;
+        q -= v ? half : 0;
+        b |= v << m;
+        m++;
+    }
+    *bits = b;
+    return m;
+}
+
+// entry e of the identifier of such a row, f the node's entry
+HMPC_HD int8_t search_block_fix(int8_t f, int e, int pos, int m, int bits) { return e >= pos && e < pos + m ? (int8_t)((bits >> (e - pos)) & 1) : f; }
+
+// the v-child of a node consumed from row r with L levels below it: where its record waits, and how many levels lie below that
+HMPC_HD int32_t search_child_srow(int32_t r, int L, int v) { return L > 0 ? r + 1 + v * search_block_rows(L - 1) : -1; }
+HMPC_HD int32_t search_child_sleft(int L) { return L > 0 ? L - 1 : 0; }
+
+// Where pick i's record is and how many levels wait below it: its waiting record, else the block staged for it (first: the
+// block's first pool row, lev: its levels).
+HMPC_HD bool search_waits(const SearchTree &t, int i) { return t.srow && t.srow[i] >= 0; }
+HMPC_HD int32_t search_pick_row(const SearchTree &t, int i, int32_t first) { return search_waits(t, i) ? t.srow[i] : first; }
+HMPC_HD int search_pick_left(const SearchTree &t, int i, int lev) { return search_waits(t, i) ? t.sleft[i] : lev; }
+
+// search_consume_pick for a record with L levels of waiting descendants below it; a refused pick (FAILED, OVERFLOW) writes
+// nothing, the waiting fields included.  The children's wrow stays the parent's row: it is used once a child without waiting
+// descendants has children of its own to launch.
+HMPC_HD int search_consume_waiting(const BranchDims &d, const SearchState &s, const SearchTree &t, int i, int32_t r, int L, int pos, double tol)
+{
+    const int32_t n = *t.n;
+    const int act = search_consume_pick(d, s, t, i, r, pos, tol);
+    if (act == SEARCH_PICK_STOP || !t.srow) return act;
+    t.srow[i] = -1;
+    if (act == SEARCH_PICK_BRANCHED)
+        for (int v = 0; v < 2; v++) {
+            t.srow[n + v] = search_child_srow(r, L, v);
+            t.sleft[n + v] = search_child_sleft(L);
+        }
+    return act;
+}
+
+// a node that begins a step (begin, adopt) has no waiting record
+HMPC_HD void search_clear_waiting(const SearchTree &t, int i)
+{
+    if (!t.srow) return;
+    t.srow[i] = -1;
+    t.sleft[i] = 0;
+}
+
 // ---- advance: the step that ended becomes the cover of the next one (hmpc_search_advance) --------------------------------------
 // Per tree what tree_retain / fleet_stage_shift / tree_adopt_shifted of hmpc_tree.h do on the host, for slabs: which leaves a tree
 // carries over, what the shift is given for each of them, and what the shift's outputs make of the tree.  The shift itself is
@@ -219,6 +297,7 @@ HMPC_HD bool search_adopt_leaf(const SearchTree &t, const SearchShift &g, int j,
     t.lb[j] = g.lb_out[b];
     t.row[j] = (int32_t)b; // (a reopened leaf carries its row too: it is solved again before anything reads it)
     t.wrow[j] = -1;        // (the records of the step that ends here are not handed down across the shift)
+    search_clear_waiting(t, j); // (nor do its waiting records survive it)
     t.alive[j] = 1;
     return (g.flags[b] & 1) != 0;
 }

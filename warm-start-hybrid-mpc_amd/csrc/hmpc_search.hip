@@ -5,16 +5,20 @@
 //   select    one workgroup per tree: `width` rounds of an argmin over the keys (lb, index) of the candidates that lie after
 //             the last pick (so no list of picked nodes is kept) -- per thread over its nodes, per wave by shuffles, the four
 //             waves through LDS.  The picks and their number are written per tree; the tree itself is not touched
+//   blocks    (speculation depth > 0 only) one wavefront per pick: pos of its identifier, hence the levels of the block it
+//             emits -- the node and its descendants through its next binaries, S(L) rows --, or -1 where its record waits
 //   offsets   ONE workgroup of 1024 threads over the trees in chunks of 1024 with a carry, as hmpc_branch_offsets_kernel: the
-//             exclusive scan of the counts -- trees in order, picks of a tree in selection order --, and one word of four for
-//             the host: the size B of the round, whether a tree has stopped FAILED / OVERFLOW, whether a node receives a
-//             record, whether rows row0 .. row0 + B - 1 fit the pool (if not, stage does nothing: the round is refused)
-//   stage     one wavefront per pick: identifier row, the tree's x0 row, the row to hand down, (tree, node); the wavefront of
-//             a running tree's first slot marks the tree DONE where it has no pick
+//             exclusive scan of the EMITTED ROWS -- trees in order, blocks of a tree in selection order --, and one word of six
+//             for the host: the size B of the round, whether a tree has stopped FAILED / OVERFLOW, whether a node receives a
+//             record, whether rows row0 .. row0 + B - 1 fit the pool (if not, stage does nothing: the round is refused), the
+//             number of picks P and how many of them are served from waiting records
+//   stage     one wavefront per emitted row: identifier row (the pick's, with the binaries of the row's pre-order index set),
+//             the tree's x0 row, the row to hand down, (tree, node); the wavefront of a running tree's first slot marks the
+//             tree DONE where it has no pick
 //   [the QP kernel writes rows row0 .. row0 + B - 1 of the pool]
 //   consume   one wavefront per tree: its picks in selection order, lane 0 carries the serial decisions
-//             (search_consume_pick: a COMPLETE pick lowers the cutoff of the next), all lanes compute pos and copy the two
-//             identifier rows of a branched node
+//             (search_consume_waiting: a COMPLETE pick lowers the cutoff of the next; the record is the pick's waiting one or
+//             the first row of its block), all lanes compute pos and copy the two identifier rows of a branched node
 // and at the end of a step: results (one wavefront per tree: the incumbent's u0, x1 and identifier, the number of leaves) and
 // leaves (one wavefront per tree: its alive nodes in list order, 64 at a time by ballot, each copied with the rows it carries),
 // or, without leaving the device, advance: retain -> offsets -> stage -> the node shift (hmpc_launch_shift) -> adopt, further down.
@@ -100,33 +104,64 @@ static __device__ __forceinline__ int32_t search_chunk_scan(int32_t v, int32_t *
     return before + incl - v;
 }
 
+// the levels of every pick's block (speculation depth > 0: they depend on pos, which takes a wavefront)
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_blocks_kernel(const BranchDims d, const SearchState s, const int width)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long slots = (long long)s.K * width;
+    for (long long q = (long long)blockIdx.x * SEARCH_WAVES + wave; q < slots; q += (long long)gridDim.x * SEARCH_WAVES) {
+        const int k = (int)(q / width), j = (int)(q % width);
+        if (j >= s.count[k]) continue; // (the same in every lane)
+        const size_t o = (size_t)k * s.node_cap + s.picks[(size_t)k * SEARCH_MAX_WIDTH + j];
+        const int pos = branch_wave_pos(s.fix + o * d.nfix, d.nfix, lane);
+        if (lane == 0) s.plev[(size_t)k * SEARCH_MAX_WIDTH + j] = search_pick_levels(s.srow[o], s.spec, d.nfix, pos);
+    }
+}
+
 __global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_offsets_kernel(const BranchDims d, const SearchState s, const int row0, const int handdown)
 {
     __shared__ int32_t totals[SEARCH_SCAN_CHUNK / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int32_t carry = 0;
+    int32_t carry = 0, picks = 0, waiting = 0;
     int bad = 0, warm = 0;
     for (int base = 0; base < s.K; base += SEARCH_SCAN_CHUNK) {
         const int k = base + tid;
         int32_t v = 0;
         if (k < s.K) {
-            v = s.count[k];
+            const int cnt = s.count[k];
             bad |= (s.state[k] & (HMPC_SEARCH_FAILED | HMPC_SEARCH_OVERFLOW)) != 0;
-            const int32_t *wrow = s.wrow + (size_t)k * s.node_cap;
-            for (int j = 0; j < v; j++) warm |= search_warm_index(wrow[s.picks[(size_t)k * SEARCH_MAX_WIDTH + j]], handdown) >= 0;
+            const size_t o = (size_t)k * s.node_cap, p = (size_t)k * SEARCH_MAX_WIDTH;
+            for (int j = 0; j < cnt; j++) { // the rows the tree emits: block after block in selection order
+                const int i = s.picks[p + j];
+                // (depth 0: a block is the node, whatever its pos -- the blocks kernel has not run)
+                const int lev = s.spec ? s.plev[p + j] : search_pick_levels(s.srow[o + i], 0, d.nfix, 0);
+                s.plev[p + j] = lev;
+                s.pfirst[p + j] = v;
+                v += search_pick_rows(lev);
+                waiting += lev < 0;
+                warm |= lev >= 0 && search_warm_index(s.wrow[o + i], handdown) >= 0;
+            }
+            picks += cnt;
         }
         int32_t chunk;
         const int32_t before = search_chunk_scan(v, totals, lane, wave, chunk);
         if (k < s.K) s.offset[k] = carry + before;
-        carry += chunk; // (at most K SEARCH_MAX_WIDTH, which hmpc_search_create holds below 2^31)
+        carry += chunk; // (emitted rows: at most K SEARCH_MAX_WIDTH S(depth), which hmpc_search_set_speculation holds below 2^31)
     }
     bad = __syncthreads_or(bad);
     warm = __syncthreads_or(warm);
+    int32_t chunk;
+    search_chunk_scan(picks, totals, lane, wave, chunk); // (the sums over the workgroup: every thread has the trees tid, tid + 1024, ...)
+    picks = chunk;
+    search_chunk_scan(waiting, totals, lane, wave, chunk);
+    waiting = chunk;
     if (tid == 0) {
         s.word[0] = carry;
         s.word[1] = bad != 0;
         s.word[2] = warm != 0;
         s.word[3] = (long long)row0 + carry <= (long long)s.row_cap;
+        s.word[4] = picks;
+        s.word[5] = waiting;
     }
 }
 
@@ -134,21 +169,27 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_stage_kernel(co
 {
     if (!s.word[3]) return; // the round does not fit the pool: nothing changes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long slots = (long long)s.K * width;
-    for (long long q = (long long)blockIdx.x * SEARCH_WAVES + wave; q < slots; q += (long long)gridDim.x * SEARCH_WAVES) {
-        const int k = (int)(q / width), j = (int)(q % width);
+    const int most = search_block_rows(s.spec); // rows of a pick's block at most: one wavefront for each of them
+    const long long slots = (long long)s.K * width * most;
+    for (long long w = (long long)blockIdx.x * SEARCH_WAVES + wave; w < slots; w += (long long)gridDim.x * SEARCH_WAVES) {
+        const int q = (int)(w % most), j = (int)((w / most) % width), k = (int)(w / most / width);
         const int cnt = s.count[k];
-        if (j == 0 && cnt == 0 && lane == 0 && search_running(s.state[k])) s.state[k] = search_done_word(s.inc[k]);
+        if (q == 0 && j == 0 && cnt == 0 && lane == 0 && search_running(s.state[k])) s.state[k] = search_done_word(s.inc[k]);
         if (j >= cnt) continue; // (the same in every lane)
-        const size_t b = (size_t)s.offset[k] + j; // < B <= row_cap - row0
+        const int lev = s.plev[(size_t)k * SEARCH_MAX_WIDTH + j];
+        if (q >= search_pick_rows(lev)) continue; // the pick's record waits, or its block is shorter
+        const size_t b = (size_t)s.offset[k] + s.pfirst[(size_t)k * SEARCH_MAX_WIDTH + j] + q; // < B <= row_cap - row0
         const int i = s.picks[(size_t)k * SEARCH_MAX_WIDTH + j];
         const int8_t *fix = s.fix + ((size_t)k * s.node_cap + i) * d.nfix;
-        for (int e = lane; e < d.nfix; e += 64) s.b_fix[b * d.nfix + e] = fix[e];
+        int bits = 0;
+        const int m = search_block_path(lev, q, &bits);
+        const int pos = m ? branch_wave_pos(fix, d.nfix, lane) : 0; // (row 0 is the node itself: nothing is set)
+        for (int e = lane; e < d.nfix; e += 64) s.b_fix[b * d.nfix + e] = search_block_fix(fix[e], e, pos, m, bits);
         for (int e = lane; e < d.nx; e += 64) s.b_x0[b * d.nx + e] = s.x0[(size_t)k * d.nx + e];
         if (lane == 0) {
-            s.b_warm[b] = search_warm_index(s.wrow[(size_t)k * s.node_cap + i], handdown);
+            s.b_warm[b] = q == 0 ? search_warm_index(s.wrow[(size_t)k * s.node_cap + i], handdown) : -1; // (a descendant's parent rides in this launch)
             s.b_tree[b] = k;
-            s.b_node[b] = i;
+            s.b_node[b] = q == 0 ? i : -1;
         }
     }
 }
@@ -167,7 +208,8 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_consume_kernel(
             int act = SEARCH_PICK_LEAF, c = 0;
             if (lane == 0) {
                 c = *t.n; // where the children go, if there are any
-                act = search_consume_pick(d, s, t, i, base + j, pos, tol);
+                const size_t p = (size_t)k * SEARCH_MAX_WIDTH + j;
+                act = search_consume_waiting(d, s, t, i, search_pick_row(t, i, base + s.pfirst[p]), search_pick_left(t, i, s.plev[p]), pos, tol);
             }
             act = __shfl(act, 0);
             c = __shfl(c, 0);
@@ -272,6 +314,7 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_begin_kernel(co
             t.lb[i] = g.offset ? g.lb[first + i] : -INFINITY;
             t.row[i] = g.offset && g.with_rows ? first + i : -1;
             t.wrow[i] = -1;
+            search_clear_waiting(t, i);
             t.alive[i] = 1;
         }
         if (lane == 0) {
@@ -413,10 +456,35 @@ struct hmpc_search {
     DevBuf<double> a_val, q_dual, q_dual_obj; // q_*: the pool the next shift writes (the two swap with every advance)
     PinBuf<double> a_hval;                    // e0 | x0_next on their way up
     PinBuf<int32_t> a_hidx;                   // word (4) | cover | reopened on their way down
+    DevBuf<int32_t> srow, sleft, plev, pfirst; // speculation: the waiting records of the nodes, the blocks of the staged picks
     int32_t row0 = 0;      // first pool row of the staged (or next) round
-    int32_t staged = 0;    // size of the staged round, 0: none
+    int32_t staged = 0;    // rows of the staged round (with waiting records a staged round may have none)
+    int32_t staged_picks = 0, staged_waiting = 0; // its picks, 0: no round is staged / those of them whose record waits
+    int64_t counters[4] = {0, 0, 0, 0}; // since begin: rounds consumed, QP launches, rows launched, picks served from waiting records
     bool begun = false;
 };
+
+// rows a round may stage at speculation depth `spec`: every pick a whole block, but never more than the pool holds
+static size_t search_batch_rows(const hmpc_search *s, int spec)
+{
+    return std::min((size_t)s->v.K * SEARCH_MAX_WIDTH * (size_t)search_block_rows(spec), (size_t)s->v.row_cap);
+}
+
+// the staging of a round for `batch` rows (hmpc_search_create, hmpc_search_set_speculation: launch paths do not allocate)
+static hipError_t search_alloc_batch(hmpc_search *s, size_t batch)
+{
+    hipError_t e;
+    if ((e = s->b_fix.alloc(batch * s->d.nfix)) != hipSuccess) return e;
+    if ((e = s->b_x0.alloc(batch * s->d.nx)) != hipSuccess) return e;
+    if ((e = s->b_idx.alloc(3 * batch)) != hipSuccess) return e;
+    int32_t *bi = s->b_idx;
+    s->v.b_fix = s->b_fix;
+    s->v.b_x0 = s->b_x0;
+    s->v.b_warm = bi;
+    s->v.b_tree = bi + batch;
+    s->v.b_node = bi + 2 * batch;
+    return hipSuccess;
+}
 
 static dim3 search_grid(long long waves)
 {
@@ -458,17 +526,18 @@ extern "C" int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, i
     HIPCHK(s->picks.alloc(k * SEARCH_MAX_WIDTH));
     HIPCHK(s->count.alloc(k));
     HIPCHK(s->offset.alloc(k));
-    HIPCHK(s->word.alloc(4));
-    HIPCHK(s->h_word.alloc(4));
-    HIPCHK(s->b_fix.alloc(batch * d.nfix));
-    HIPCHK(s->b_x0.alloc(batch * d.nx));
-    HIPCHK(s->b_idx.alloc(3 * batch));
+    HIPCHK(s->word.alloc(6));
+    HIPCHK(s->h_word.alloc(6));
+    HIPCHK(s->srow.alloc(nodes));
+    HIPCHK(s->sleft.alloc(nodes));
+    HIPCHK(s->plev.alloc(k * SEARCH_MAX_WIDTH));
+    HIPCHK(s->pfirst.alloc(k * SEARCH_MAX_WIDTH));
     int32_t *ti = s->ti;
     double *td = s->td;
-    int32_t *bi = s->b_idx;
     s->v = SearchState{K, node_cap, row_cap, s->fix, s->lb, s->row, s->wrow, s->alive, ti, ti + k, ti + 2 * k, ti + 3 * k, ti + 4 * k, ti + 5 * k,
                        td, td + k, s->x0, s->p_obj, s->p_dual_obj, s->p_status, s->p_iters, s->p_primal, s->p_dual, s->picks, s->count, s->offset, s->word,
-                       s->b_fix, s->b_x0, bi, bi + batch, bi + 2 * batch};
+                       nullptr, nullptr, nullptr, nullptr, nullptr, s->srow, s->sleft, s->plev, s->pfirst, 0};
+    HIPCHK(search_alloc_batch(s.get(), batch));
     *out = s.release();
     return HMPC_OK;
 }
@@ -523,8 +592,27 @@ extern "C" int hmpc_search_begin(hmpc_search *s, const double *x0, const int32_t
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));
     s->row0 = dual ? (int32_t)total : 0;
-    s->staged = 0;
+    s->staged = s->staged_picks = s->staged_waiting = 0;
+    std::fill(s->counters, s->counters + 4, (int64_t)0);
     s->begun = true;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_set_speculation(hmpc_search *s, int32_t depth)
+{
+    g_err.clear();
+    if (depth < 0 || depth > SEARCH_MAX_SPEC) return fail(HMPC_EINVAL, "search: the speculation depth must lie in 0 .. 4");
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    if ((long long)s->v.K * SEARCH_MAX_WIDTH * search_block_rows(depth) >= (1ll << 31))
+        return fail(HMPC_EINVAL, "search: K too large for this depth (a round's rows are indexed with int32)");
+    const size_t batch = search_batch_rows(s, depth);
+    if (batch > s->b_idx.size() / 3) { // (a shallower depth keeps the larger staging)
+        HIPCHK(hipSetDevice(s->h->device));
+        HIPCHK(hipDeviceSynchronize()); // (nothing that reads the old staging is in flight)
+        HIPCHK(search_alloc_batch(s, batch));
+    }
+    s->v.spec = depth;
     return HMPC_OK;
 }
 
@@ -537,20 +625,45 @@ extern "C" int hmpc_search_select(hmpc_search *s, int32_t width, double tol, int
     HIPCHK(hipSetDevice(s->h->device));
     hipStream_t st = (hipStream_t)stream;
     const int hd = handdown != 0;
-    s->staged = 0;
+    s->staged = s->staged_picks = s->staged_waiting = 0;
+    const long long slots = (long long)s->v.K * width, most = search_block_rows(s->v.spec);
     hipLaunchKernelGGL(hmpc_search_select_kernel, dim3(s->v.K), dim3(SEARCH_SELECT_THREADS), 0, st, s->d, s->v, (int)width, tol);
     HIPCHK(hipGetLastError());
+    if (s->v.spec > 0) {
+        hipLaunchKernelGGL(hmpc_search_blocks_kernel, search_grid(slots), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, (int)width);
+        HIPCHK(hipGetLastError());
+    }
     hipLaunchKernelGGL(hmpc_search_offsets_kernel, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->d, s->v, (int)s->row0, hd);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hmpc_search_stage_kernel, search_grid((long long)s->v.K * width), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, (int)width, hd);
+    hipLaunchKernelGGL(hmpc_search_stage_kernel, search_grid(slots * most), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, (int)width, hd);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_word, s->word, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s->h_word, s->word, 6 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const int32_t *w = s->h_word;
-    if (w[0] < 0 || (long long)w[0] > (long long)s->v.K * width) return fail(HMPC_EDEVICE, "search: the device returned a round size outside [0, K width]");
+    if (w[0] < 0 || (long long)w[0] > slots * most) return fail(HMPC_EDEVICE, "search: the device returned a round size outside [0, K width S(depth)]");
+    if (w[4] < 0 || (long long)w[4] > slots || w[5] < 0 || w[5] > w[4]) return fail(HMPC_EDEVICE, "search: the device returned a number of picks outside [0, K width]");
     *B = w[0];
     if (!w[3]) return fail(HMPC_ETOOBIG, "search: the round's records do not fit the pool (row_cap)");
     s->staged = w[0];
+    s->staged_picks = w[4];
+    s->staged_waiting = w[5];
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_staged(const hmpc_search *s, int32_t *picks, int32_t *B)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (picks) *picks = s->staged_picks;
+    if (B) *B = s->staged;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_counters(const hmpc_search *s, int64_t *out)
+{
+    g_err.clear();
+    if (!s || !out) return fail(HMPC_EINVAL, "search: null argument");
+    std::copy(s->counters, s->counters + 4, out);
     return HMPC_OK;
 }
 
@@ -591,12 +704,16 @@ extern "C" int hmpc_search_consume(hmpc_search *s, double tol, void *stream)
 {
     g_err.clear();
     if (!s) return fail(HMPC_EINVAL, "search: null search");
-    if (s->staged <= 0) return fail(HMPC_EINVAL, "search: no round is staged (hmpc_search_select)");
+    if (s->staged_picks <= 0) return fail(HMPC_EINVAL, "search: no round is staged (hmpc_search_select)");
     HIPCHK(hipSetDevice(s->h->device));
     hipLaunchKernelGGL(hmpc_search_consume_kernel, search_grid((long long)s->v.K), dim3(64 * SEARCH_WAVES), 0, (hipStream_t)stream, s->d, s->v, (int)s->row0, tol);
     HIPCHK(hipGetLastError());
+    s->counters[0]++;
+    s->counters[1] += s->staged > 0;
+    s->counters[2] += s->staged;
+    s->counters[3] += s->staged_waiting;
     s->row0 += s->staged;
-    s->staged = 0;
+    s->staged = s->staged_picks = s->staged_waiting = 0;
     return HMPC_OK;
 }
 
@@ -610,14 +727,16 @@ extern "C" int hmpc_search_run(hmpc_search *s, int32_t width, double tol, int32_
         int32_t B = 0;
         int rc = hmpc_search_select(s, width, tol, handdown, &B, stream);
         if (rc) return rc;
-        if (B == 0) break;
-        const double *x0;
-        const int8_t *fix;
-        hmpc_warm warm;
-        hmpc_result rows;
-        hmpc_search_batch(s, &x0, &fix, &warm, &rows, nullptr);
-        // (as the host-pointer solve does: the hand-down kernel only where a node of the round receives a record)
-        if ((rc = hmpc_solve_batch_device(s->h, x0, s->d.nx, fix, B, s->h_word[2] ? &warm : nullptr, &rows, stream))) return rc;
+        if (s->staged_picks == 0) break; // (no pick: every tree has stopped)
+        if (B > 0) { // (else every pick's record waits: a round without a launch)
+            const double *x0;
+            const int8_t *fix;
+            hmpc_warm warm;
+            hmpc_result rows;
+            hmpc_search_batch(s, &x0, &fix, &warm, &rows, nullptr);
+            // (as the host-pointer solve does: the hand-down kernel only where a node of the round receives a record)
+            if ((rc = hmpc_solve_batch_device(s->h, x0, s->d.nx, fix, B, s->h_word[2] ? &warm : nullptr, &rows, stream))) return rc;
+        }
         if ((rc = hmpc_search_consume(s, tol, stream))) return rc;
         if (rounds) ++*rounds;
         if (launched) *launched += B;
@@ -709,7 +828,7 @@ extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const doubl
     g_err.clear();
     if (!s) return fail(HMPC_EINVAL, "search: null search");
     if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
-    if (s->staged > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
     if (!s->h->dp.shift_Mmu) return fail(HMPC_EINVAL, "search: hmpc_set_shift_maps has not been called");
     HIPCHK(hipSetDevice(s->h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -754,7 +873,7 @@ extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const doubl
     s->v.p_dual = s->p_dual;
     s->v.p_dual_obj = s->p_dual_obj;
     s->row0 = B;
-    s->staged = 0;
+    s->staged = s->staged_picks = s->staged_waiting = 0;
     if (cover || reopened) {
         HIPCHK(hipMemcpyAsync(down + 4, a.cover, 2 * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -802,6 +921,19 @@ extern "C" int hmpc_search_tree(hmpc_search *s, int32_t k, int32_t *scalars6, do
     if (row) HIPCHK(hipMemcpy(row, v.row + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (wrow) HIPCHK(hipMemcpy(wrow, v.wrow + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (alive) HIPCHK(hipMemcpy(alive, v.alive + o, n, hipMemcpyDeviceToHost));
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_tree_waiting(hmpc_search *s, int32_t k, int32_t *srow, int32_t *sleft)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (k < 0 || k >= s->v.K) return fail(HMPC_EINVAL, "search: no such tree");
+    HIPCHK(hipSetDevice(s->h->device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t o = (size_t)k * s->v.node_cap, n = (size_t)s->v.node_cap;
+    if (srow) HIPCHK(hipMemcpy(srow, s->v.srow + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sleft) HIPCHK(hipMemcpy(sleft, s->v.sleft + o, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return HMPC_OK;
 }
 

@@ -24,9 +24,15 @@ class DeviceSearch(object):
 
     node_cap : nodes a tree may hold (a tree that needs more stops with the OVERFLOW state)
     row_cap  : rows of the record pool, one per solved node of a step and one per leaf of the covers (default K * node_cap)
+    speculation : depth s in 0 .. 4 (``set_speculation``).  Every picked node that has to be launched rides with all its
+               descendants through its next s binaries; their records wait in the pool, and a later pick of such a descendant
+               costs no launch.  With ``handdown=False`` the searches are those of s = 0 bit for bit, in fewer launches; with
+               hand-down on the descendants are solved cold and results agree to the solver's tolerance only.  A step then needs
+               up to 2^(s+1) - 1 pool rows per launched pick instead of one: the default ``row_cap`` stays, so give a larger
+               one where ``SearchTooBig`` is raised.
     """
 
-    def __init__(self, controller, K, node_cap=1024, row_cap=None):
+    def __init__(self, controller, K, node_cap=1024, row_cap=None, speculation=0):
         qp = controller.qp
         if not hasattr(qp, 'handle') or not hasattr(qp, 'lib'):
             raise RuntimeError('DeviceSearch needs the HIP backend (the product path has no CPU fallback).')
@@ -41,6 +47,10 @@ class DeviceSearch(object):
             raise (ValueError if rc == -1 else RuntimeError)('hmpc_search_create failed (%d): %s' % (rc, qp.lib.hmpc_last_error().decode()))
         self._s = s
         self.rounds, self.launched = 0, 0
+        self._B = self._P = 0
+        self.speculation = 0
+        if speculation:
+            self.set_speculation(speculation)
 
     def __del__(self):
         s = getattr(self, '_s', None)
@@ -52,6 +62,21 @@ class DeviceSearch(object):
         if rc == -3:
             raise SearchTooBig(self.qp.lib.hmpc_last_error().decode())
         self.qp._check(rc)
+
+    def set_speculation(self, depth):
+        """Speculation depth of the rounds to come, 0 .. 4; not while a round is staged.  Waiting records stay valid."""
+        rc = self.qp.lib.hmpc_search_set_speculation(self._s, int(depth))
+        if rc == -1:
+            raise ValueError('hmpc_search_set_speculation failed: %s' % self.qp.lib.hmpc_last_error().decode())
+        self._check(rc)
+        self.speculation = int(depth)
+
+    def counters(self):
+        """Since ``begin``: dict rounds, launches (rounds that launched QPs), rows (nodes launched), served (picks consumed
+        from waiting records)."""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self.qp.lib.hmpc_search_counters(self._s, out))
+        return dict(zip(('rounds', 'launches', 'rows', 'served'), (int(v) for v in out)))
 
     # ------------------------------------------------------------------
     def begin(self, x0s, warm_starts=None):
@@ -75,12 +100,16 @@ class DeviceSearch(object):
                                                   dual.ctypes.data, dobj.ctypes.data))
 
     def select(self, frontier_width=8, tol=0., handdown=True, stream=None):
-        """Stages the next round and returns its size (0: every tree has stopped) -- the one synchronisation of a round.
+        """Stages the next round and returns its size B, the rows to solve -- the one synchronisation of a round.  The number
+        of picks is in ``self._P``: the search has stopped when it is 0 (without speculation that is B == 0; with it a round
+        whose picks all have waiting records has B == 0 and is still consumed).
         Raises ``SearchTooBig``, with nothing changed, when the round's records do not fit the pool."""
-        B = ctypes.c_int32()
+        B, P = ctypes.c_int32(), ctypes.c_int32()
+        self._B = self._P = 0
         self._check(self.qp.lib.hmpc_search_select(self._s, int(frontier_width), float(tol), int(bool(handdown)), ctypes.byref(B),
                                                    ctypes.c_void_p(stream)))
-        self._B = B.value
+        self._check(self.qp.lib.hmpc_search_staged(self._s, ctypes.byref(P), None))
+        self._B, self._P = B.value, P.value
         return B.value
 
     def batch(self, device=False):
@@ -131,10 +160,11 @@ class DeviceSearch(object):
 
     def consume(self, tol=0., stream=None):
         self._check(self.qp.lib.hmpc_search_consume(self._s, float(tol), ctypes.c_void_p(stream)))
-        self._B = 0
+        self._B = self._P = 0
 
     def run(self, frontier_width=8, tol=0., handdown=True, max_rounds=0, stream=None):
-        """select -> solve -> consume until every tree has stopped.  Returns (rounds, nodes launched)."""
+        """select -> solve -> consume until every tree has stopped.  Returns (rounds, nodes launched); ``counters()`` says how
+        many of the rounds launched QPs."""
         r, n = ctypes.c_int32(), ctypes.c_int64()
         self._check(self.qp.lib.hmpc_search_run(self._s, int(frontier_width), float(tol), int(bool(handdown)), int(max_rounds),
                                                 ctypes.c_void_p(stream), ctypes.byref(r), ctypes.byref(n)))
@@ -194,18 +224,20 @@ class DeviceSearch(object):
         self._check(self.qp.lib.hmpc_search_advance(self._s, None if e0 is None else e0.ctypes.data, None if xn is None else xn.ctypes.data,
                                                     out['cover'].ctypes.data if stats else None, out['reopened'].ctypes.data if stats else None,
                                                     ctypes.c_void_p(stream)))
-        self._B = 0
+        self._B = self._P = 0
         return out
 
     def tree(self, k):
-        """Tree k as it stands (for inspection): scalars and the whole slab, node_cap entries each."""
+        """Tree k as it stands (for inspection): scalars and the whole slab, node_cap entries each (srow, sleft: the pool row
+        of a node's waiting record or -1, the levels of waiting descendants below it)."""
         nc = self.node_cap
         sc, bd = np.empty(6, dtype=np.int32), np.empty(2)
         out = dict(fix=np.empty((nc, self.nfix), dtype=np.int8), lb=np.empty(nc), row=np.empty(nc, dtype=np.int32), wrow=np.empty(nc, dtype=np.int32),
                    alive=np.empty(nc, dtype=np.uint8))
         self._check(self.qp.lib.hmpc_search_tree(self._s, int(k), sc.ctypes.data, bd.ctypes.data, *[out[q].ctypes.data for q in ('fix', 'lb', 'row', 'wrow', 'alive')]))
         out.update(zip(('n', 'inc', 'inc_row', 'solves', 'uncertified', 'state'), (int(v) for v in sc)))
-        out.update(ub=bd[0], unc_lb=bd[1])
+        out.update(ub=bd[0], unc_lb=bd[1], srow=np.empty(nc, dtype=np.int32), sleft=np.empty(nc, dtype=np.int32))
+        self._check(self.qp.lib.hmpc_search_tree_waiting(self._s, int(k), out['srow'].ctypes.data, out['sleft'].ctypes.data))
         return out
 
     # ------------------------------------------------------------------
