@@ -3236,7 +3236,18 @@ DEV int ipm_solve(const DevProb &p, const Lds &S, Rows<RS> &R, RM &rm, int lane,
                 ROWS_BEGIN(k, rw)
                     const double d = R.D(k, rw.e);
                     double v = d * rm.h(p, S, k, rw); // right-hand side of the constant direction
-                    if (mode != 0) v = d >= 1.0 ? v - R.dz(k, rw.e) : d * R.dz(k, rw.e);
+                    if (mode != 0) {
+                        // (hand-down: a handed node enters these passes without an interior-point pass of its own, so the dz
+                        // slot of a row that takes no part -- the bounds of a binary the node fixes, D = 0 -- holds what the
+                        // workgroup's previous node or the previous launch left in the register.  0 * that is no number where
+                        // that is none: the NaN stayed in S.e, the sweeps never saw it (a fixed binary is prescribed), the fixed
+                        // binary's multiplier, read off its stationarity row after the solve, came out NaN and write_record
+                        // split it by sign into two zeros -- nu_lb / nu_ub of a verified hand-down 0 in one launch, 30 .. 60 in
+                        // the next.  Such a row takes 0.  A cold node has written every slot in its first iteration; the cold
+                        // kernels keep the product: their code is what it was.)
+                        if constexpr (WARM) v = d >= 1.0 ? v - R.dz(k, rw.e) : d != 0.0 ? d * R.dz(k, rw.e) : 0.0;
+                        else v = d >= 1.0 ? v - R.dz(k, rw.e) : d * R.dz(k, rw.e);
+                    }
                     S.e[rw.e] = v;
                 ROWS_END
                 if (mode == 2)
