@@ -143,6 +143,31 @@ int hmpc_search_leaves(hmpc_search *s, int32_t *n, int32_t *owner, int8_t *fix, 
  * One readback (12 bytes) is the only synchronisation when cover and reopened are NULL. */
 int hmpc_search_advance(hmpc_search *s, const double *e0, const double *x0_next, int32_t *cover, int32_t *reopened, void *stream);
 
+/* The trees as they stand are carried to a neighbouring initial state of the SAME stage, on the device: x0_new (K x nx, host).
+ * x0 enters a node's QP only through the right-hand side of x_0 = x0, so every record's multipliers stay dual feasible at any
+ * x0 and its dual (or Farkas) objective moves by exactly -lam_0 . (x0_new - x0), lam_0 the first nx entries of its dual row
+ * (the run-time half of the reference's construct_warm_start, controller.py:541-558, without the time shift).  A search solved
+ * for the PREDICTED next state while the plant moves is thereby a complete proof tree for the measured one, bounds moved by
+ * O(|x0_new - x0|): advance(e0 = NULL) -> run [idle time] -> rebase(measured state) -> run.
+ * cover, reopened (K each, host, nullable): leaves tree k keeps / how many of them carry no usable bound.
+ * Requires a begun step and no staged round; hmpc_set_shift_maps is NOT needed.
+ * A tree takes part if and only if its state has neither FAILED nor OVERFLOW -- a RUNNING tree (state 0) does: the search need
+ * not have ended.  Every other tree becomes its root at the new state, as hmpc_search_begin with count == NULL leaves it
+ * (cover 0, reopened 0).  Of a tree that takes part ALL alive nodes are kept, in list order; kept leaf j of tree k becomes node
+ * j with its identifier unchanged and row first[k] + j of the pool, whose rows 0 .. B - 1 are verbatim copies of the dual rows
+ * the leaves carried (B: all kept leaves; the pools swap as in an advance, so the pool is compacted and the next round's records
+ * begin at row B); a node without a row (row < 0) gets the row of zeros and counts as reopened.  With r the row a leaf carried,
+ * delta = x0_new[k] - x0[k], and every product and sum rounded on its own (no fma), j = 0 .. nx - 1 in order:
+ *   dot = sum_j dual[r][j] * delta[j];  obj = max(dual_obj[r] - dot, 0);  the new row's dual_obj = obj
+ *   lb not infinite: lb' = obj;   lb infinite and obj <= 0: lb' = 0, reopened;   lb infinite and obj > 0: lb' = lb
+ * (the tail of both shift kernels, isinf and all; a weak record, dual_obj = -inf, reopens an infeasible leaf).
+ * Nothing is handed down across a re-base (wrow = -1) and waiting speculative records are dropped (srow = -1, sleft = 0).
+ * Every tree then has the scalars of a fresh begin -- ub = +inf, no incumbent, state 0, solves and uncertified 0 --, the counters
+ * of hmpc_search_counters start from zero, and x0 = x0_new.
+ * HMPC_EINVAL without touching the GPU: null search or x0_new.  HMPC_ETOOBIG: B > row_cap, with nothing changed.
+ * One readback (12 bytes) is the only synchronisation when cover and reopened are NULL. */
+int hmpc_search_rebase(hmpc_search *s, const double *x0_new, int32_t *cover, int32_t *reopened, void *stream);
+
 /* Host copies, for a caller that solves the staged round elsewhere and for inspection (each synchronises; any array NULL).
  * get_batch: the staged round (B: its size) -- x0 (B x nx), fix (B x T*nub), the rows handed down, and the (tree, node) of
  *   every pick.

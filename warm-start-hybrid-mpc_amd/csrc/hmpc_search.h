@@ -2,7 +2,8 @@
 //
 // Plain inline functions that compile for the device (hipcc) and for the host (g++), as hmpc_branch.h does: which nodes are
 // candidates and in which order they are picked, what consuming ONE pick does to its tree, and what the end of a step does to it
-// (hmpc_search_advance: which leaves it keeps, what the shift is given for them, what adoption makes of the tree).  Every decision
+// (hmpc_search_advance: which leaves it keeps, what the shift is given for them, what adoption makes of the tree) or a move to a
+// neighbouring initial state (hmpc_search_rebase: which trees take part, how a row's dual objective and a leaf's bound move).  Every decision
 // about a record is a function of hmpc_branch.h (branch_word, branch_child_lb, branch_child_warm; pos from branch_pos_*): nothing
 // of it is restated here.  The kernels (hmpc_search.hip) supply the workgroup argmin, the scan over the trees and the lane loops over
 // identifier rows; tests/host/search_driver.cpp and advance_driver.cpp walk the same functions serially under AddressSanitizer.
@@ -315,6 +316,76 @@ HMPC_HD void search_adopt_scalars(const SearchState &s, const SearchTree &t, int
     *t.state = agreed ? 0 : HMPC_SEARCH_FAILED;
     s.count[k] = 0;
     s.offset[k] = 0;
+}
+
+// ---- rebase: the trees of a step are carried to a neighbouring initial state of the SAME stage (hmpc_search_rebase) -------------
+// x0 enters a node's QP only through the right-hand side of x_0 = x0, so every record's multipliers stay dual feasible and its dual
+// (or Farkas) objective moves by -lam_0 . (x0_new - x0): the tail of both shift kernels (hmpc_shift.hip; controller.py:541-558),
+// without the time shift.  retain -> offsets -> stage -> rebase-rows -> adopt share the staging of SearchShift with the advance:
+// stage and adopt of a leaf ARE search_stage_leaf and search_adopt_leaf (flags bit 0 is always set here: nothing is dropped).
+
+// a tree takes part if and only if it has neither failed nor outgrown its slab; a running tree does
+HMPC_HD bool search_rebases(int32_t state) { return (state & (HMPC_SEARCH_FAILED | HMPC_SEARCH_OVERFLOW)) == 0; }
+
+// retain rule: every alive node of a tree that takes part
+HMPC_HD bool search_rebase_retained(uint8_t alive) { return alive != 0; }
+
+// serial form of one tree's retain, as search_retain_serial
+HMPC_HD int search_rebase_retain_serial(const SearchTree &t, int32_t *keep)
+{
+    if (!search_rebases(*t.state)) return 0;
+    int cnt = 0;
+    for (int i = 0; i < *t.n; i++)
+        if (search_rebase_retained(t.alive[i])) keep[cnt++] = i;
+    return cnt;
+}
+
+// The dual objective of a row at the new state: dual_obj - lam_0 . (x0_new - x0), clamped at 0 as the shift clamps it.  lam_0 is
+// the row's first nx entries.  Serial, every product and every sum rounded on its own (no fma: the result is the same float64 on
+// the host, on the device and in numpy).
+// (The library is built with -ffp-contract=fast, under which the device back end fuses a product into a sum whatever a pragma says:
+// on the device the product is made opaque before it is added -- an empty asm, no instruction.  The host builds with contraction off.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SEARCH_ROUNDED(v) asm volatile("" : "+v"(v))
+#else
+#define SEARCH_ROUNDED(v) ((void)0)
+#endif
+HMPC_HD double search_rebase_obj(const double *dual, double dual_obj, const double *x0_new, const double *x0, int nx)
+{
+    double dot = 0.0;
+    for (int j = 0; j < nx; j++) {
+        const double delta = x0_new[j] - x0[j];
+        double prod = dual[j] * delta;
+        SEARCH_ROUNDED(prod);
+        dot = dot + prod;
+    }
+    const double obj = dual_obj - dot;
+    return obj > 0.0 ? obj : 0.0;
+}
+
+// the bound of a kept leaf from the bound it had and its row's new dual objective (the shift kernels' rule, their isinf test
+// quoted); *flag: bit 0 kept, bit 1 reopened -- the flags of the shift
+HMPC_HD double search_rebase_bound(double lb, double obj, uint8_t *flag)
+{
+    *flag = 1;
+    double nlb;
+    if (!isinf(lb)) nlb = obj;                       // a solved / bounded leaf: its bound is the moved dual objective
+    else if (obj <= 0.0) { nlb = 0.0; *flag |= 2; } // the infeasibility proof did not survive: reopen
+    else nlb = lb;                                   // still proved infeasible
+    return nlb;
+}
+
+// a tree that does not take part becomes its root, as hmpc_search_begin without a cover leaves node 0 (its identifier row: all
+// SEARCH_ROOT_FIX); returns the number of its nodes
+#define SEARCH_ROOT_FIX ((int8_t)-1)
+HMPC_HD int search_rebase_root(const SearchTree &t)
+{
+    t.lb[0] = -INFINITY;
+    t.row[0] = -1;
+    t.wrow[0] = -1;
+    search_clear_waiting(t, 0);
+    t.alive[0] = 1;
+    return 1;
 }
 
 #endif // HMPC_SEARCH_CORE_H

@@ -21,7 +21,9 @@
 //             the first row of its block), all lanes compute pos and copy the two identifier rows of a branched node
 // and at the end of a step: results (one wavefront per tree: the incumbent's u0, x1 and identifier, the number of leaves) and
 // leaves (one wavefront per tree: its alive nodes in list order, 64 at a time by ballot, each copied with the rows it carries),
-// or, without leaving the device, advance: retain -> offsets -> stage -> the node shift (hmpc_launch_shift) -> adopt, further down.
+// or, without leaving the device, advance: retain -> offsets -> stage -> the node shift (hmpc_launch_shift) -> adopt, further down;
+// and rebase (the trees carried to a neighbouring state of the same stage): the same kernels under a compile-time switch around
+// rebase-rows, one wavefront per kept leaf.
 // Memory bound and small; nothing is staged in LDS but the four partial minima.  Plain C++ stores only: every store is a vector store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -335,19 +337,23 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_begin_kernel(co
 // ---- advance: retain -> offsets -> stage -> [hmpc_launch_shift] -> adopt (arithmetic: hmpc_search.h) ---------------------------
 // retain   one wavefront per tree: its nodes 64 at a time, each lane tests its own node's stage-0 entries against the incumbent's
 //          input; the kept nodes go into the tree's index list in list order (ballot, rank = kept lanes below), with their number
+//          (REBASE: every alive node of a tree that takes part -- search_rebases, search_rebase_retained)
+template <bool REBASE>
 __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_retain_kernel(const BranchDims d, const SearchState s, const SearchShift g)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
         const SearchTree t = search_tree(s, d.nfix, k);
         int cnt = 0;
-        if (search_advances(*t.state)) { // (the same in every lane)
+        if (REBASE ? search_rebases(*t.state) : search_advances(*t.state)) { // (the same in every lane)
             const int n = *t.n;
-            const double *u0 = search_incumbent_u0(d, s, t);
+            const double *u0 = REBASE ? nullptr : search_incumbent_u0(d, s, t);
             int32_t *keep = g.keep + (size_t)k * s.node_cap;
             for (int base = 0; base < n; base += 64) {
                 const int mine = base + lane;
-                const bool kept = mine < n && t.alive[mine] != 0 && search_retained(d, t.fix + (size_t)mine * d.nfix, u0);
+                bool kept = mine < n;
+                if constexpr (REBASE) kept = kept && search_rebase_retained(t.alive[mine < n ? mine : 0]);
+                else kept = kept && t.alive[mine] != 0 && search_retained(d, t.fix + (size_t)mine * d.nfix, u0);
                 const unsigned long long m = __ballot(kept);
                 if (kept) keep[cnt + __popcll(m & ((1ull << lane) - 1))] = mine; // < n <= node_cap
                 cnt += __popcll(m);
@@ -358,6 +364,8 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_retain_kernel(c
 }
 
 // offsets  ONE workgroup: where every tree's kept leaves begin (the scan of the rounds' offsets kernel), and the word the host reads
+//          (REBASE: a running tree is no refusal)
+template <bool REBASE>
 __global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_advance_offsets_kernel(const SearchState s, const SearchShift g)
 {
     __shared__ int32_t totals[SEARCH_SCAN_CHUNK / 64];
@@ -379,25 +387,29 @@ __global__ void __launch_bounds__(SEARCH_SCAN_CHUNK) hmpc_search_advance_offsets
     running = __syncthreads_or(running);
     if (tid == 0) {
         g.word[0] = carry;
-        g.word[1] = running != 0;
+        g.word[1] = !REBASE && running != 0;
         g.word[2] = carry <= s.row_cap;
     }
 }
 
 // stage    one wavefront per tree: what the shift reads -- per kept leaf its tree, the row it carries, its bound and its identifier,
 //          per tree the applied input and the next state (given != 0: the caller's, already in place)
+//          (REBASE: the kept leaves only -- no input is applied, and the new state is always the caller's)
+template <bool REBASE>
 __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_advance_stage_kernel(const BranchDims d, const SearchState s, const SearchShift g, const int given)
 {
     if (g.word[1] || !g.word[2]) return; // refused: a tree is running, or the leaves do not fit the pool
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
         const SearchTree t = search_tree(s, d.nfix, k);
-        const bool adv = search_advances(*t.state);
-        const double *w = adv ? s.p_primal + (size_t)*t.inc_row * d.n_primal : nullptr;
-        for (int e = lane; e < d.nu; e += 64) g.u0[(size_t)k * d.nu + e] = search_stage_u0(adv ? w + d.o_u : nullptr, adv, e);
-        if (!given)
-            for (int e = lane; e < d.nx; e += 64)
-                g.x0_next[(size_t)k * d.nx + e] = search_stage_x0(w, d.nx, adv, s.x0[(size_t)k * d.nx + e], g.e0[(size_t)k * d.nx + e], e);
+        if constexpr (!REBASE) {
+            const bool adv = search_advances(*t.state);
+            const double *w = adv ? s.p_primal + (size_t)*t.inc_row * d.n_primal : nullptr;
+            for (int e = lane; e < d.nu; e += 64) g.u0[(size_t)k * d.nu + e] = search_stage_u0(adv ? w + d.o_u : nullptr, adv, e);
+            if (!given)
+                for (int e = lane; e < d.nx; e += 64)
+                    g.x0_next[(size_t)k * d.nx + e] = search_stage_x0(w, d.nx, adv, s.x0[(size_t)k * d.nx + e], g.e0[(size_t)k * d.nx + e], e);
+        }
         const int cnt = g.kept[k];
         const size_t first = (size_t)g.first[k]; // first + cnt <= B <= row_cap
         const int32_t *keep = g.keep + (size_t)k * s.node_cap;
@@ -411,6 +423,8 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_advance_stage_k
 
 // adopt    one wavefront per tree: the shifted leaves are the tree (it reads the staging and the shift's outputs only, never the
 //          slab it overwrites); cover and reopened by shuffles; a kept leaf the shift dropped stops the tree
+//          (REBASE: the identifiers are the staged ones, copied; a tree that does not take part becomes its root; no tree fails)
+template <bool REBASE>
 __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_adopt_kernel(const BranchDims d, const SearchState s, const SearchShift g)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -418,21 +432,75 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_adopt_kernel(co
         const SearchTree t = search_tree(s, d.nfix, k);
         const int cnt = g.kept[k]; // <= the tree's nodes <= node_cap
         const size_t first = (size_t)g.first[k];
-        int dropped = 0, reop = 0;
+        const int8_t *ident = REBASE ? g.fix : g.fix_out;
+        int dropped = 0, reop = 0, n = cnt;
         for (int j = lane; j < cnt; j += 64) {
             dropped |= !search_adopt_leaf(t, g, j, first + j);
             reop += search_leaf_reopened(s, g, first + j);
         }
         for (int j = 0; j < cnt; j++)
-            for (int e = lane; e < d.nfix; e += 64) t.fix[(size_t)j * d.nfix + e] = g.fix_out[(first + j) * d.nfix + e];
+            for (int e = lane; e < d.nfix; e += 64) t.fix[(size_t)j * d.nfix + e] = ident[(first + j) * d.nfix + e];
+        if (REBASE && !search_rebases(*t.state)) { // (the same in every lane; cnt == 0: the retain kept nothing of it)
+            if (lane == 0) n = search_rebase_root(t);
+            n = __shfl(n, 0);
+            for (int e = lane; e < d.nfix; e += 64) t.fix[e] = SEARCH_ROOT_FIX;
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) reop += __shfl_xor(reop, o);
-        dropped = __any(dropped);
+        dropped = !REBASE && __any(dropped);
         for (int e = lane; e < d.nx; e += 64) s.x0[(size_t)k * d.nx + e] = g.x0_next[(size_t)k * d.nx + e];
         if (lane == 0) {
-            search_adopt_scalars(s, t, k, cnt, !dropped);
+            search_adopt_scalars(s, t, k, n, !dropped);
             g.cover[k] = cnt;
             g.reopened[k] = reop;
+        }
+    }
+}
+
+// ---- rebase: retain<true> -> offsets<true> -> stage<true> -> rebase-rows -> adopt<true> (arithmetic: hmpc_search.h) -------------
+// rebase-rows  one wavefront per staged leaf, grid-strided: the leaf's dual row crosses HBM once each way, verbatim, into row b of
+//          the OTHER pool -- 16 bytes per lane and access where n_dual is even (every row then starts on a 16-byte boundary of
+//          its pool), else 8 --, SEARCH_COPY_BATCH independent loads in flight before their stores, every output entry stored once;
+//          lane 0 carries the bound: nx serial products against the row's lam_0, search_rebase_obj / search_rebase_bound.
+//          No LDS, no workgroup barrier: a wave owns its row.  B: the staged leaves (<= row_cap; src[b] <= row_cap, the zero row).
+#define SEARCH_COPY_BATCH 4
+template <class V>
+static __device__ __forceinline__ void search_copy_row(const V *__restrict__ in, V *__restrict__ out, const int n, const int lane)
+{
+    for (int j0 = 0; j0 < n; j0 += 64 * SEARCH_COPY_BATCH) {
+        V v[SEARCH_COPY_BATCH];
+#pragma unroll
+        for (int u = 0; u < SEARCH_COPY_BATCH; u++) {
+            const int j = j0 + u * 64 + lane;
+            v[u] = in[j < n ? j : n - 1]; // (no predicate on the load: a lane beyond the end reads the last entry again and stores nothing)
+        }
+#pragma unroll
+        for (int u = 0; u < SEARCH_COPY_BATCH; u++) {
+            const int j = j0 + u * 64 + lane;
+            if (j < n) out[j] = v[u];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_rebase_rows_kernel(const BranchDims d, const SearchState s, const SearchShift g, const int B,
+                                                                                    double *__restrict__ q_dual, double *__restrict__ q_dual_obj)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nd = d.n_dual;
+    for (long long w = (long long)blockIdx.x * SEARCH_WAVES + wave; w < B; w += (long long)gridDim.x * SEARCH_WAVES) {
+        const size_t b = (size_t)w;
+        const int32_t r = g.src[b];
+        const double *in = s.p_dual + (size_t)r * nd;
+        double *out = q_dual + b * nd;
+        if ((nd & 1) == 0) search_copy_row((const double2 *)in, (double2 *)out, nd >> 1, lane);
+        else search_copy_row(in, out, nd, lane);
+        if (lane == 0) {
+            const size_t k = (size_t)g.owner[b];
+            const double obj = search_rebase_obj(in, s.p_dual_obj[r], g.x0_next + k * d.nx, s.x0 + k * d.nx, d.nx);
+            uint8_t flag;
+            g.lb_out[b] = search_rebase_bound(g.lb[b], obj, &flag);
+            g.flags[b] = flag;
+            q_dual_obj[b] = obj;
         }
     }
 }
@@ -847,11 +915,11 @@ extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const doubl
         HIPCHK(hipMemcpyAsync(a.x0_next, up + state, state * sizeof(double), hipMemcpyHostToDevice, st));
     }
     const dim3 trees = search_grid((long long)K), waves(64 * SEARCH_WAVES);
-    hipLaunchKernelGGL(hmpc_search_retain_kernel, trees, waves, 0, st, d, s->v, a);
+    hipLaunchKernelGGL(hmpc_search_retain_kernel<false>, trees, waves, 0, st, d, s->v, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hmpc_search_advance_offsets_kernel, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->v, a);
+    hipLaunchKernelGGL(hmpc_search_advance_offsets_kernel<false>, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->v, a);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(hmpc_search_advance_stage_kernel, trees, waves, 0, st, d, s->v, a, (int)(x0_next != nullptr));
+    hipLaunchKernelGGL(hmpc_search_advance_stage_kernel<false>, trees, waves, 0, st, d, s->v, a, (int)(x0_next != nullptr));
     HIPCHK(hipGetLastError());
     int32_t *down = s->a_hidx;
     HIPCHK(hipMemcpyAsync(down, a.word, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -865,7 +933,7 @@ extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const doubl
                           a.fix_out, a.lb_out, s->q_dual, s->q_dual_obj, a.flags};
         if ((rc = hmpc_launch_shift(s->h, g, st))) return rc;
     }
-    hipLaunchKernelGGL(hmpc_search_adopt_kernel, trees, waves, 0, st, d, s->v, a);
+    hipLaunchKernelGGL(hmpc_search_adopt_kernel<false>, trees, waves, 0, st, d, s->v, a);
     HIPCHK(hipGetLastError());
     // the pools swap: rows 0 .. B - 1 of the next step's pool are the shifted leaves'
     std::swap(s->p_dual, s->q_dual);
@@ -874,6 +942,60 @@ extern "C" int hmpc_search_advance(hmpc_search *s, const double *e0, const doubl
     s->v.p_dual_obj = s->p_dual_obj;
     s->row0 = B;
     s->staged = s->staged_picks = s->staged_waiting = 0;
+    if (cover || reopened) {
+        HIPCHK(hipMemcpyAsync(down + 4, a.cover, 2 * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (cover) std::copy(down + 4, down + 4 + K, cover);
+        if (reopened) std::copy(down + 4 + K, down + 4 + 2 * K, reopened);
+    }
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_rebase(hmpc_search *s, const double *x0_new, int32_t *cover, int32_t *reopened, void *stream)
+{
+    g_err.clear();
+    if (!s || !x0_new) return fail(HMPC_EINVAL, "search: null argument (the search and x0_new are required)");
+    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    HIPCHK(hipSetDevice(s->h->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc = search_advance_setup(s, st);
+    if (rc) return rc;
+    const BranchDims &d = s->d;
+    const SearchShift &a = s->a;
+    const size_t K = (size_t)s->v.K, state = K * d.nx;
+    // x0_new through the pinned block, where an advance's x0_next goes (the readback below is behind the copy)
+    double *up = s->a_hval;
+    up += state;
+    std::copy(x0_new, x0_new + state, up);
+    HIPCHK(hipMemcpyAsync(a.x0_next, up, state * sizeof(double), hipMemcpyHostToDevice, st));
+    const dim3 trees = search_grid((long long)K), waves(64 * SEARCH_WAVES);
+    hipLaunchKernelGGL(hmpc_search_retain_kernel<true>, trees, waves, 0, st, d, s->v, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_advance_offsets_kernel<true>, dim3(1), dim3(SEARCH_SCAN_CHUNK), 0, st, s->v, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(hmpc_search_advance_stage_kernel<true>, trees, waves, 0, st, d, s->v, a, 1);
+    HIPCHK(hipGetLastError());
+    int32_t *down = s->a_hidx;
+    HIPCHK(hipMemcpyAsync(down, a.word, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // the one synchronisation: how many rows are re-based, and whether they fit
+    const int32_t B = down[0];
+    if (B < 0 || (long long)B > (long long)K * s->v.node_cap) return fail(HMPC_EDEVICE, "search: the device returned a number of kept leaves outside [0, K node_cap]");
+    if (!down[2]) return fail(HMPC_ETOOBIG, "search: the kept leaves do not fit the pool (row_cap)");
+    if (B > 0) {
+        hipLaunchKernelGGL(hmpc_search_rebase_rows_kernel, search_grid((long long)B), waves, 0, st, d, s->v, a, (int)B, (double *)s->q_dual, (double *)s->q_dual_obj);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(hmpc_search_adopt_kernel<true>, trees, waves, 0, st, d, s->v, a);
+    HIPCHK(hipGetLastError());
+    // the pools swap: rows 0 .. B - 1 of the pool from here on are the kept leaves', compact
+    std::swap(s->p_dual, s->q_dual);
+    std::swap(s->p_dual_obj, s->q_dual_obj);
+    s->v.p_dual = s->p_dual;
+    s->v.p_dual_obj = s->p_dual_obj;
+    s->row0 = B;
+    s->staged = s->staged_picks = s->staged_waiting = 0;
+    std::fill(s->counters, s->counters + 4, (int64_t)0);
     if (cover || reopened) {
         HIPCHK(hipMemcpyAsync(down + 4, a.cover, 2 * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));

@@ -178,7 +178,7 @@ def load_library():
                            ('hmpc_search_put_records', [vp, i32, ctypes.POINTER(_Result)]), ('hmpc_search_consume', [vp, ctypes.c_double, vp]),
                            ('hmpc_search_run', [vp, i32, ctypes.c_double, i32, i32, vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
                            ('hmpc_search_results', [vp] * 9), ('hmpc_search_leaves', [vp, _ip] + [vp] * 6),
-                           ('hmpc_search_advance', [vp] * 6),
+                           ('hmpc_search_advance', [vp] * 6), ('hmpc_search_rebase', [vp] * 5),
                            ('hmpc_search_get_batch', [vp, i32] + [vp] * 5), ('hmpc_search_tree', [vp, i32] + [vp] * 7),
                            ('hmpc_search_rows', [vp, i32, i32, ctypes.POINTER(_Result), i32]),
                            ('hmpc_search_set_speculation', [vp, i32]), ('hmpc_search_staged', [vp, _ip, _ip]),
@@ -200,7 +200,7 @@ EXPORTED_SYMBOLS = ('hmpc_create', 'hmpc_destroy', 'hmpc_record_sizes', 'hmpc_la
 # include/hmpc_search.h (a header of its own: include/hmpc.h is part of the key of every compiled kernel)
 EXPORTED_SEARCH_SYMBOLS = ('hmpc_search_create', 'hmpc_search_destroy', 'hmpc_search_begin', 'hmpc_search_select', 'hmpc_search_batch',
                            'hmpc_search_put_records', 'hmpc_search_consume', 'hmpc_search_run', 'hmpc_search_results', 'hmpc_search_leaves',
-                           'hmpc_search_advance', 'hmpc_search_get_batch', 'hmpc_search_tree', 'hmpc_search_rows',
+                           'hmpc_search_advance', 'hmpc_search_rebase', 'hmpc_search_get_batch', 'hmpc_search_tree', 'hmpc_search_rows',
                            'hmpc_search_set_speculation', 'hmpc_search_staged', 'hmpc_search_counters', 'hmpc_search_tree_waiting')
 SEARCH_STATES = dict(done=0x1, incumbent=0x2, failed=0x4, overflow=0x8)
 

@@ -227,6 +227,21 @@ class DeviceSearch(object):
         self._B = self._P = 0
         return out
 
+    def rebase(self, x0s, stats=True, stream=None):
+        """The trees as they stand are carried to the states x0s (K, nx) of the same stage (``hmpc_search_rebase``): every alive
+        node of a tree that has neither failed nor overflowed stays, its bound moved by -lam_0 . (x0_new - x0) of the dual row it
+        carries; the other trees become their roots.  Running trees take part.  Needs no shift maps.  Returns dict cover,
+        reopened (K each) -- or, with ``stats=False``, None and one synchronisation less.  Raises ``SearchTooBig``, with nothing
+        changed, when the kept leaves outnumber the pool."""
+        x0s = np.ascontiguousarray(np.atleast_2d(x0s), dtype=np.float64)
+        if x0s.shape != (self.K, self.nx):
+            raise ValueError('x0s must have shape (%d, %d).' % (self.K, self.nx))
+        out = dict(cover=np.empty(self.K, dtype=np.int32), reopened=np.empty(self.K, dtype=np.int32)) if stats else None
+        self._check(self.qp.lib.hmpc_search_rebase(self._s, x0s.ctypes.data, out['cover'].ctypes.data if stats else None,
+                                                   out['reopened'].ctypes.data if stats else None, ctypes.c_void_p(stream)))
+        self._B = self._P = 0
+        return out
+
     def tree(self, k):
         """Tree k as it stands (for inspection): scalars and the whole slab, node_cap entries each (srow, sleft: the pool row
         of a node's waiting record or -1, the levels of waiting descendants below it)."""
@@ -297,19 +312,80 @@ class DeviceSearch(object):
         stats.update(steps=steps, wall=perf_counter() - tic)
         return stats
 
-    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True, resident=False):
+    def _raise_if_stopped(self, r):
+        bad = r['state'] & (SEARCH_STATES['failed'] | SEARCH_STATES['overflow'])
+        if np.any(bad & SEARCH_STATES['failed']):
+            raise RuntimeError('QP solver did not converge on a node of %d searches' % int(((bad & SEARCH_STATES['failed']) != 0).sum()))
+        if np.any(bad):
+            raise RuntimeError('%d trees outgrew node_cap = %d' % (int((bad != 0).sum()), self.node_cap))
+
+    def _closed_loop_presolve(self, x0s, n_steps, errors, frontier_width, tol, handdown):
+        """``closed_loop`` with the search moved into the idle time between an input and the next measurement: after step t's
+        ``results`` the trees ``advance`` to the PREDICTED state x1 (no error) and ``run`` there while the plant moves; on the
+        measurement x1 + e_t they ``rebase`` and ``run`` again -- from a complete proof tree whose bounds moved by O(|e_t|) -- and
+        only that second run and its ``results`` stand between the measurement and the input.  An idle-time search that stops
+        FAILED or OVERFLOW costs nothing but its head start: the re-base makes such a tree its root."""
+        K = self.K
+        zeros = lambda: np.zeros((K, n_steps), np.int64)
+        stats = dict(nodes_ws=zeros(), len_ws=zeros(), reopened=zeros(), costs=np.full((K, n_steps), np.nan), nodes_pre=zeros(), nodes_rt=zeros(),
+                     reopened_rt=zeros(), rounds_rt=np.zeros(n_steps, np.int64), time_rt=np.zeros(n_steps), time_pre=np.zeros(n_steps))
+        alive = np.ones(K, dtype=bool)
+        xs = x0s.copy()
+        tic = perf_counter()
+        steps = 0
+        if n_steps > 0:
+            t0 = perf_counter()
+            self.begin(xs)
+            stats['rounds_rt'][0], _ = self.run(frontier_width, tol, handdown)
+            r = self.results()
+            stats['time_rt'][0] = perf_counter() - t0
+            self._raise_if_stopped(r)
+            stats['nodes_rt'][:, 0] = stats['nodes_ws'][:, 0] = r['solves']
+        for t in range(n_steps):
+            alive &= np.isfinite(r['cost'])
+            if not alive.any():
+                break
+            t0 = perf_counter()
+            a = self.advance(None)                                  # (to the model's next state: the measurement is not there yet)
+            stats['len_ws'][alive, t], stats['reopened'][alive, t], stats['costs'][alive, t] = a['cover'][alive], a['reopened'][alive], r['cost'][alive]
+            steps += int(alive.sum())
+            if t + 1 == n_steps:
+                break
+            self.run(frontier_width, tol, handdown)                 # the idle-time search
+            pre = self.results()
+            stats['time_pre'][t + 1] = perf_counter() - t0
+            xs[alive] = r['x1'][alive] + errors[alive, t]           # the measurement
+            t0 = perf_counter()
+            b = self.rebase(xs)
+            stats['rounds_rt'][t + 1], _ = self.run(frontier_width, tol, handdown)
+            r = self.results()
+            stats['time_rt'][t + 1] = perf_counter() - t0
+            self._raise_if_stopped(r)
+            stats['nodes_pre'][alive, t + 1], stats['nodes_rt'][alive, t + 1], stats['reopened_rt'][alive, t + 1] = pre['solves'][alive], r['solves'][alive], b['reopened'][alive]
+            stats['nodes_ws'][alive, t + 1] = pre['solves'][alive] + r['solves'][alive]
+        stats.update(steps=steps, wall=perf_counter() - tic)
+        return stats
+
+    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True, resident=False, presolve=False):
         """K closed loops from the same x0 (or from K states, (K, nx)) under prescribed model errors (K, n_steps, nx), as
         ``FleetMPC.closed_loop``: per step ``run``, then the leaves go through the backend's node shift (``hmpc_shift_batch``) and
         become the covers of ``begin``.  ``resident=True``: the same walk with the step boundary on the device (``advance``) -- no
         leaf, identifier or dual row crosses the bus.
+        ``presolve=True`` (implies the resident path): every step after the first is searched twice -- in the idle time at the
+        model's predicted state, then, re-based to the measured one (``rebase``), again; see ``_closed_loop_presolve``.
         A loop whose MIQP is infeasible ends (its tree stays empty).  Returns dict of arrays (K, n_steps): nodes_ws, len_ws,
-        reopened, costs (NaN where a loop has ended), steps, wall."""
+        reopened, costs (NaN where a loop has ended), steps, wall.  With ``presolve`` also nodes_pre (solves of the idle-time run),
+        nodes_rt and rounds_rt (n_steps: solves and rounds after the re-base -- what the controller waits for; step 0: the cold
+        search), reopened_rt (leaves the re-base reopened), time_pre and time_rt (n_steps, seconds: advance + idle-time run /
+        re-base to results); nodes_ws is then nodes_pre + nodes_rt."""
         from .batched import BatchedMPC
         bm = BatchedMPC(self.c)                                 # (uploads the shift's maps)
         K = self.K
         errors = np.asarray(errors, dtype=np.float64)
         xs = np.asarray(x0, dtype=np.float64)
         xs = np.repeat(xs[None], K, axis=0) if xs.ndim == 1 else xs.copy()
+        if presolve:
+            return self._closed_loop_presolve(xs, n_steps, errors, frontier_width, tol, handdown)
         if resident:
             return self._closed_loop_resident(xs, n_steps, errors, frontier_width, tol, handdown)
         ws = None
