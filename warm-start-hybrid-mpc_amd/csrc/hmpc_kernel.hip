@@ -71,6 +71,9 @@
 #ifndef HMPC_NARROW_PANEL // (0: diagnostic builds without the narrow panel of stages whose binaries are all fixed)
 #define HMPC_NARROW_PANEL 1
 #endif
+#ifndef HMPC_NARROW_STAGE // (0: A/B builds in which a stage whose binaries are all fixed runs factor_reg's full-width body)
+#define HMPC_NARROW_STAGE 1
+#endif
 #define HMPC_POLISH_ATTEMPTS 3 // per solve: a node whose active set resists is left to the interior-point iterate
 #define HMPC_RETRY (-1) // internal: a hand-down attempt with the terminal-set rows did not verify, run the regular sequence
 #define HMPC_POLISH_ROUNDS_WARM 3 // active sets tried when the set is handed down by the parent node
@@ -1585,85 +1588,154 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                 for (int l = 0; l < NX; l++) a += bcast16<D>(pn[l < i ? l : i], l < i ? i : l) * ABc[l]; // P_{t+1}(i, l), symmetric
                 y[i] = a;
             }
-            double col[NZ];
+            double col[NZ], myrow[NU], dinv[NU];
+            // A stage whose binaries are ALL fixed by the node (half of the stage steps of a search: branching fixes stage by
+            // stage) has an (NX + NUC)-wide block: rows and pivots of the binaries are prescribed.  Its body forms, assembles and
+            // eliminates the rows i < NX + NUC only; what it leaves in Lm, dinv and Pr is what the full-width body leaves there.
+            // The entries of S.g at the prescribed components are read by nothing (the sweeps override them): zero.
+            if (HMPC_NARROW_STAGE && NUB > 0 && __builtin_amdgcn_readfirstlane((int)((S.fullfix >> t) & 1ull))) {
+              constexpr int NR = NX + NUC;
 #pragma unroll
-            for (int i = 0; i < NZ; i++) {
-                double a = 0.0;
+              for (int i = 0; i < NR; i++) {
+                  double a = 0.0;
 #pragma unroll
-                for (int l = 0; l < NX; l++) a += S.AB[l * NZ + i] * y[l]; // (a uniform LDS read: as a cross-lane broadcast the 44
-                                                                         // constants are hoisted out of every loop and live in registers for good)
-                col[i] = a;
-            }
-            FSTAMP(0);
-            // (3) + P + C' D C (this wave wrote it: LDS operations of one wave complete in order)
-            if (lane < NZ) {
+                  for (int l = 0; l < NX; l++) a += S.AB[l * NZ + i] * y[l];
+                  col[i] = a;
+              }
+              FSTAMP(0);
+              if (lane < NZ) {
 #pragma unroll
-                for (int i = 0; i < NZ; i++) col[i] += S.Mm[i * NZ + lane];
-                if (S.term_on && t == T - 1) {
+                  for (int i = 0; i < NR; i++) col[i] += S.Mm[i * NZ + lane];
+                  if (S.term_on && t == T - 1) {
 #pragma unroll
-                    for (int i = 0; i < NZ; i++) col[i] += TG[i * NZ + lane];
-                }
+                      for (int i = 0; i < NR; i++) col[i] += TG[i * NZ + lane];
+                  }
+              } else {
+#pragma unroll
+                  for (int i = 0; i < NR; i++) col[i] = 0.0;
+              }
+              FSTAMP(1);
+              int nones = 0;
+#pragma unroll
+              for (int b = 0; b < NUB; b++) nones += __builtin_amdgcn_readfirstlane(fxv[b]) == 1;
+              if (nones) {
+                  double mbv[NR];
+#pragma unroll
+                  for (int i = 0; i < NR; i++) mbv[i] = 0.0;
+#pragma unroll
+                  for (int b = 0; b < NUB; b++)
+                      if (__builtin_amdgcn_readfirstlane(fxv[b]) == 1) {
+#pragma unroll
+                          for (int i = 0; i < NR; i++) mbv[i] += bcast16<D>(col[i], NR + b);
+                      }
+                  if (lane == 0) {
+#pragma unroll
+                      for (int i = 0; i < NR; i++) S.g[t * NZ + i] = mbv[i];
+                  }
+                  if (lane >= NR && lane < NZ) S.g[t * NZ + lane] = 0.0;
+              } else if (lane < NZ) {
+                  S.g[t * NZ + lane] = 0.0;
+              }
+              // the binaries' columns: identity (their rows >= NR are never formed)
+#pragma unroll
+              for (int i = 0; i < NR; i++) col[i] = lane >= NR ? 0.0 : col[i];
+              FSTAMP(2);
+#pragma unroll
+              for (int j = 0; j < NUC; j++) {
+                  const int pj = NX + j;
+                  const double d = bcast16<D>(col[pj], pj);
+                  if (!(d > 0.0)) bad = 1;
+                  double rinv = __builtin_amdgcn_rcp(d);
+                  rinv = rinv * (2.0 - d * rinv);
+                  dinv[j] = rinv;
+                  const double cr = col[pj] * rinv;
+                  myrow[j] = (lane < NX || lane > pj) ? cr : 0.0;
+#pragma unroll
+                  for (int i = 0; i < NR; i++) {
+                      if (i < NX || i > pj) col[i] -= bcast16<D>(col[i], pj) * cr;
+                  }
+              }
+#pragma unroll
+              for (int j = NUC; j < NU; j++) { myrow[j] = 0.0; dinv[j] = 1.0; }
             } else {
 #pragma unroll
-                for (int i = 0; i < NZ; i++) col[i] = 0.0;
-            }
-            FSTAMP(1);
-            int nfixed = 0;
+              for (int i = 0; i < NZ; i++) {
+                  double a = 0.0;
 #pragma unroll
-            for (int b = 0; b < NUB; b++) nfixed += fxv[b] >= 0;
-            if (nfixed) {
-                // columns of binaries fixed to one (for the constant direction), before prescribing
-                double mbv[NZ];
+                  for (int l = 0; l < NX; l++) a += S.AB[l * NZ + i] * y[l]; // (a uniform LDS read: as a cross-lane broadcast the 44
+                                                                           // constants are hoisted out of every loop and live in registers for good)
+                  col[i] = a;
+              }
+              FSTAMP(0);
+              // (3) + P + C' D C (this wave wrote it: LDS operations of one wave complete in order)
+              if (lane < NZ) {
 #pragma unroll
-                for (int i = 0; i < NZ; i++) mbv[i] = 0.0;
+                  for (int i = 0; i < NZ; i++) col[i] += S.Mm[i * NZ + lane];
+                  if (S.term_on && t == T - 1) {
 #pragma unroll
-                for (int b = 0; b < NUB; b++)
-                    if (fxv[b] == 1) {
+                      for (int i = 0; i < NZ; i++) col[i] += TG[i * NZ + lane];
+                  }
+              } else {
 #pragma unroll
-                        for (int i = 0; i < NZ; i++) mbv[i] += bcast16<D>(col[i], NX + NUC + b);
-                    }
-                if (lane == 0) {
+                  for (int i = 0; i < NZ; i++) col[i] = 0.0;
+              }
+              FSTAMP(1);
+              int nfixed = 0;
 #pragma unroll
-                    for (int i = 0; i < NZ; i++) S.g[t * NZ + i] = mbv[i];
-                }
+              for (int b = 0; b < NUB; b++) nfixed += fxv[b] >= 0;
+              if (nfixed) {
+                  // columns of binaries fixed to one (for the constant direction), before prescribing
+                  double mbv[NZ];
 #pragma unroll
-                for (int b = 0; b < NUB; b++)
-                    if (fxv[b] >= 0) {
-                        const int cb = NX + NUC + b;
+                  for (int i = 0; i < NZ; i++) mbv[i] = 0.0;
 #pragma unroll
-                        for (int i = 0; i < NZ; i++)
-                            col[i] = (lane == cb) ? (i == cb ? 1.0 : 0.0) : (i == cb ? 0.0 : col[i]);
-                    }
-            } else if (lane < NZ) {
-                S.g[t * NZ + lane] = 0.0;
-            }
-            FSTAMP(2);
-            // The multiplier of row i at pivot j is M(i, pj) / d; by symmetry lane i holds it as
-            // col[pj] / d, so every lane keeps the multipliers of its own row and stores them once.
-            double myrow[NU], dinv[NU];
-            auto pivot = [&](const int j) {
-                const int pj = NX + j;
-                const double d = bcast16<D>(col[pj], pj); // 1 at a prescribed pivot: the step below changes nothing
-                if (!(d > 0.0)) bad = 1;
-                double rinv = __builtin_amdgcn_rcp(d);
-                rinv = rinv * (2.0 - d * rinv);
-                dinv[j] = rinv;
-                const double cr = col[pj] * rinv;
-                myrow[j] = (lane < NX || lane > pj) ? cr : 0.0;
+                  for (int b = 0; b < NUB; b++)
+                      if (fxv[b] == 1) {
 #pragma unroll
-                for (int i = 0; i < NZ; i++) {
-                    if (i < NX || i > pj) col[i] -= bcast16<D>(col[i], pj) * cr; // rows still to be reduced
-                }
-            };
+                          for (int i = 0; i < NZ; i++) mbv[i] += bcast16<D>(col[i], NX + NUC + b);
+                      }
+                  if (lane == 0) {
 #pragma unroll
-            for (int j = 0; j < NUC; j++) pivot(j);
-            // a stage whose binaries are all fixed (most stages of a deep node): their pivot steps are no-ops
-            if ((S.fullfix >> t) & 1ull) {
+                      for (int i = 0; i < NZ; i++) S.g[t * NZ + i] = mbv[i];
+                  }
 #pragma unroll
-                for (int j = NUC; j < NU; j++) { myrow[j] = 0.0; dinv[j] = 1.0; }
-            } else {
+                  for (int b = 0; b < NUB; b++)
+                      if (fxv[b] >= 0) {
+                          const int cb = NX + NUC + b;
 #pragma unroll
-                for (int j = NUC; j < NU; j++) pivot(j);
+                          for (int i = 0; i < NZ; i++)
+                              col[i] = (lane == cb) ? (i == cb ? 1.0 : 0.0) : (i == cb ? 0.0 : col[i]);
+                      }
+              } else if (lane < NZ) {
+                  S.g[t * NZ + lane] = 0.0;
+              }
+              FSTAMP(2);
+              // The multiplier of row i at pivot j is M(i, pj) / d; by symmetry lane i holds it as
+              // col[pj] / d, so every lane keeps the multipliers of its own row and stores them once.
+              auto pivot = [&](const int j) {
+                  const int pj = NX + j;
+                  const double d = bcast16<D>(col[pj], pj); // 1 at a prescribed pivot: the step below changes nothing
+                  if (!(d > 0.0)) bad = 1;
+                  double rinv = __builtin_amdgcn_rcp(d);
+                  rinv = rinv * (2.0 - d * rinv);
+                  dinv[j] = rinv;
+                  const double cr = col[pj] * rinv;
+                  myrow[j] = (lane < NX || lane > pj) ? cr : 0.0;
+#pragma unroll
+                  for (int i = 0; i < NZ; i++) {
+                      if (i < NX || i > pj) col[i] -= bcast16<D>(col[i], pj) * cr; // rows still to be reduced
+                  }
+              };
+#pragma unroll
+              for (int j = 0; j < NUC; j++) pivot(j);
+              // a stage whose binaries are all fixed (most stages of a deep node): their pivot steps are no-ops
+              if ((S.fullfix >> t) & 1ull) {
+#pragma unroll
+                  for (int j = NUC; j < NU; j++) { myrow[j] = 0.0; dinv[j] = 1.0; }
+              } else {
+#pragma unroll
+                  for (int j = NUC; j < NU; j++) pivot(j);
+              }
             }
             if (lane < NZ) { // rows of the states: NU entries; row i of the inputs: its i entries (zeros at skipped pivots)
                 ldsd *row = Lm + (lane < NX ? lane * NU : LM_U(NX, NU, lane - NX, 0));
