@@ -73,7 +73,12 @@ def active_set_primal(ctrl, dq, x0, fix, dual_row):
     r = int((s > 1e-10 * s[0]).sum())
     wp = Vt[:r].T @ ((U[:, :r].T @ beq) / s[:r])
     Z = Vt[r:].T
-    y = np.linalg.lstsq(Z.T @ H @ Z, -Z.T @ (H @ wp), rcond=1e-13)[0]
+    # Curvature below 1e-13 of the cost's own is rounding: the cutoff is relative to |H|, not to the largest curvature left in the
+    # null space.  Where the active set leaves the cost nothing to choose (short horizons: Z'HZ ~ 1e-34 throughout) a cutoff
+    # relative to that noise divided by it, and the "solution" left the equalities by order one.
+    K = Z.T @ H @ Z
+    hn, kn = np.linalg.norm(H, 2), np.linalg.norm(K, 2) if K.size else 0.
+    y = np.linalg.lstsq(K, -Z.T @ (H @ wp), rcond=1e-13 * hn / kn)[0] if kn > 1e-13 * hn else np.zeros(Z.shape[1])
     w = wp + Z @ y
     return w, np.max(np.abs(Aeq @ w - beq))
 

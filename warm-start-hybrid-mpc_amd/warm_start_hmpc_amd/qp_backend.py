@@ -367,17 +367,20 @@ class HipBatchedQP(object):
         out['iters'] = out['iters'] & 0xFFFF
         return out
 
-    def solve_batch_device(self, x0, fix, out, stream=None, warm=None):
+    def solve_batch_device(self, x0, fix, out, stream=None, warm=None, x0_stride=None):
         """Device-resident form: torch CUDA tensors in and out, asynchronous on ``stream``
         (default: torch's current stream).  ``out`` is a dict of preallocated tensors with keys
         obj, dual_obj (float64 [B]), status, iters (int32 [B]), primal [B, n_primal], dual [B, n_dual]
         (the last two may be None).  ``warm``: optional (primal rows, dual rows, int32 index [B]) CUDA tensors, the
-        hand-down of ``hmpc_warm`` (the rows must not be rows of ``out``)."""
+        hand-down of ``hmpc_warm`` (the rows must not be rows of ``out``).  ``x0_stride``: doubles between the states of
+        consecutive nodes in ``x0`` (the ``x0_stride`` of the C ABI: states inside wider rows); default 0 for one shared
+        state, ``nx`` for a [B, nx] tensor."""
         import torch
         B = fix.shape[0]
         assert fix.dtype == torch.int8 and fix.is_cuda and fix.is_contiguous() and fix.shape[1] == self.nfix
         assert x0.dtype == torch.float64 and x0.is_cuda and x0.is_contiguous()
-        stride = 0 if x0.dim() == 1 else self.nx
+        stride = (0 if x0.dim() == 1 else self.nx) if x0_stride is None else int(x0_stride)
+        assert x0.numel() >= max(0, (B - 1) * stride) + self.nx or 0 < stride < self.nx     # (a stride below nx the library refuses)
         res = _Result(**{k: (out[k].data_ptr() if out.get(k) is not None else None)
                          for k in ('obj', 'dual_obj', 'status', 'iters', 'primal', 'dual')})
         if stream is None:
