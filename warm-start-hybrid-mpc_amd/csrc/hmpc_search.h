@@ -15,7 +15,7 @@
 #ifndef HMPC_SEARCH_CORE_H
 #define HMPC_SEARCH_CORE_H
 
-#include "../../include/hmpc_search.h"
+#include "../../include/hmpc_search_anytime.h" // (includes hmpc_search.h)
 #include "hmpc_branch.h"
 
 #define SEARCH_MAX_WIDTH 64 // picks per tree and round at most: the stride of a tree's picks
@@ -41,6 +41,10 @@ struct SearchState {
     int32_t *srow, *sleft;                // K node_cap: pool row of the node's own waiting record or -1 / levels of waiting descendants below it
     int32_t *plev, *pfirst;               // the staged round, K x SEARCH_MAX_WIDTH: levels of a launched pick's block (-1: its record waits) / first row of the block within its tree's rows
     int spec;                             // speculation depth, 0 .. SEARCH_MAX_SPEC
+    // anytime searches (include/hmpc_search_anytime.h; at the end again, and zeros mean rule 0 and no budget)
+    int rule;                             // HMPC_RULE_*
+    int budget1;                          // max_solves + 1; 0: no budget
+    int32_t *open;                        // K: the staged round found the tree with candidates and no budget left (null: no budgets)
 };
 
 struct SearchTree { // one tree of it
@@ -100,6 +104,85 @@ HMPC_HD int search_select_serial(const SearchTree &t, int width, double tol, int
 
 // state of a tree that has no candidate left
 HMPC_HD int32_t search_done_word(int32_t inc) { return HMPC_SEARCH_DONE | (inc >= 0 ? HMPC_SEARCH_INCUMBENT : 0); }
+
+// ---- anytime: the rule's order, the budgeted selection, the stop word, the bound of a tree (include/hmpc_search_anytime.h) --------
+// All rules are ONE order over keys (first, index) under search_key_less / search_take: first = the bound (best-first), -index
+// (depth-first: the largest index comes first) or index (breadth-first).  An index is exact as a double, and no key of the two
+// index rules is -inf, the key before the first pick.
+HMPC_HD int search_tree_rule(int rule, int32_t inc)
+{
+    if (rule != HMPC_RULE_DIVE_THEN_BEST) return rule;
+    return inc < 0 ? HMPC_RULE_DEPTH_FIRST : HMPC_RULE_BEST_FIRST;
+}
+
+// (rule: what search_tree_rule returns -- one of the first three)
+HMPC_HD double search_rule_key(int rule, double lb, int i)
+{
+    return rule == HMPC_RULE_DEPTH_FIRST ? -(double)i : rule == HMPC_RULE_BREADTH_FIRST ? (double)i : lb;
+}
+
+// picks a running tree may stage: min(width, max_solves - solves), width without a budget
+HMPC_HD int search_pick_limit(int width, int budget1, int32_t solves)
+{
+    if (budget1 <= 0) return width;
+    const int left = budget1 - 1 - solves;
+    return left < 0 ? 0 : left < width ? left : width;
+}
+
+// Serial form of one tree's selection under a rule and a budget (the kernel runs the same functions over a workgroup).  With the
+// budget exhausted ONE candidate is still looked for and none is picked: *open says whether the tree has candidates and no budget.
+HMPC_HD int search_select_anytime(const SearchTree &t, int rule, int budget1, int width, double tol, int32_t *picks, int32_t *open)
+{
+    *open = 0;
+    if (!search_running(*t.state)) return 0;
+    const int n = *t.n, order = search_tree_rule(rule, *t.inc), limit = search_pick_limit(width, budget1, *t.solves);
+    const int probe = limit > 0 ? limit : 1;
+    const double ub = *t.ub;
+    double pk = -INFINITY;
+    int pi = -1, found = 0;
+    while (found < probe) {
+        double bk = 0.0;
+        int bi = -1;
+        for (int i = 0; i < n; i++) {
+            const double key = search_rule_key(order, t.lb[i], i);
+            if (search_candidate(t.alive[i], t.lb[i], ub, tol) && search_take(bk, bi, key, i, pk, pi)) { bk = key; bi = i; }
+        }
+        if (bi < 0) break;
+        if (found < limit) picks[found] = bi;
+        found++;
+        pk = bk;
+        pi = bi;
+    }
+    const int cnt = found < limit ? found : limit;
+    *open = found > cnt;
+    return cnt;
+}
+
+// state of a running tree that stages no pick: out of budget with candidates left, or done
+HMPC_HD int32_t search_stop_word(int32_t inc, int32_t open)
+{
+    return open ? HMPC_SEARCH_BUDGET | (inc >= 0 ? HMPC_SEARCH_INCUMBENT : 0) : search_done_word(inc);
+}
+
+// hmpc_search_set_budget lets exactly these trees run again
+HMPC_HD bool search_budget_stopped(int32_t state) { return (state & ~HMPC_SEARCH_INCUMBENT) == HMPC_SEARCH_BUDGET; }
+
+// the smaller of two bounds; a NaN b is skipped (a is never NaN: it starts from +inf)
+HMPC_HD double search_bound_min(double a, double b) { return b < a ? b : a; }
+
+// serial form of what a tree proves: *lower = min(min over alive nodes of lb, unc_lb), *open = its candidates at tol
+HMPC_HD void search_bounds_serial(const SearchTree &t, double tol, double *lower, int32_t *open)
+{
+    double lo = INFINITY;
+    int32_t cand = 0;
+    const double ub = *t.ub;
+    for (int i = 0; i < *t.n; i++) {
+        if (t.alive[i]) lo = search_bound_min(lo, t.lb[i]);
+        cand += search_candidate(t.alive[i], t.lb[i], ub, tol);
+    }
+    *lower = search_bound_min(lo, *t.unc_lb);
+    *open = cand;
+}
 
 // the row a picked node receives from its parent
 HMPC_HD int32_t search_warm_index(int32_t wrow, int handdown) { return handdown ? wrow : -1; }
@@ -243,8 +326,12 @@ struct SearchShift {
     int32_t *cover, *reopened;            // K each
 };
 
-// a tree advances if and only if its search ended with an incumbent and nothing else
-HMPC_HD bool search_advances(int32_t state) { return state == (HMPC_SEARCH_DONE | HMPC_SEARCH_INCUMBENT); }
+// a tree advances if and only if its search ended with an incumbent and nothing else -- proved (DONE) or cut off by its budget: the
+// leaves of an unfinished tree still cover the binary cube, and every bound in it is still a dual bound
+HMPC_HD bool search_advances(int32_t state)
+{
+    return state == (HMPC_SEARCH_DONE | HMPC_SEARCH_INCUMBENT) || state == (HMPC_SEARCH_BUDGET | HMPC_SEARCH_INCUMBENT);
+}
 
 // retain rule (tree_retain; both shift kernels): entry q < nub of an identifier against the incumbent's q-th binary of stage 0
 HMPC_HD bool search_retain_item(int8_t f, double u) { return f < 0 || f == (int)rint(u); }

@@ -4,7 +4,9 @@
 // host as well; this file supplies the lane loops, the reductions, the scan and the stores.  Per round, on the caller's stream:
 //   select    one workgroup per tree: `width` rounds of an argmin over the keys (lb, index) of the candidates that lie after
 //             the last pick (so no list of picked nodes is kept) -- per thread over its nodes, per wave by shuffles, the four
-//             waves through LDS.  The picks and their number are written per tree; the tree itself is not touched
+//             waves through LDS.  The picks and their number are written per tree; the tree itself is not touched.
+//             (include/hmpc_search_anytime.h: under another rule the key's first entry is -index or index, the same loop; under a
+//             budget the rounds are min(width, budget left), and a tree without budget looks for one candidate it does not pick)
 //   blocks    (speculation depth > 0 only) one wavefront per pick: pos of its identifier, hence the levels of the block it
 //             emits -- the node and its descendants through its next binaries, S(L) rows --, or -1 where its record waits
 //   offsets   ONE workgroup of 1024 threads over the trees in chunks of 1024 with a carry, as hmpc_branch_offsets_kernel: the
@@ -14,7 +16,7 @@
 //             number of picks P and how many of them are served from waiting records
 //   stage     one wavefront per emitted row: identifier row (the pick's, with the binaries of the row's pre-order index set),
 //             the tree's x0 row, the row to hand down, (tree, node); the wavefront of a running tree's first slot marks the
-//             tree DONE where it has no pick
+//             tree DONE where it has no pick (out of BUDGET where select found it with candidates and no budget left)
 //   [the QP kernel writes rows row0 .. row0 + B - 1 of the pool]
 //   consume   one wavefront per tree: its picks in selection order, lane 0 carries the serial decisions
 //             (search_consume_waiting: a COMPLETE pick lowers the cutoff of the next; the record is the pick's waiting one or
@@ -45,18 +47,22 @@ __global__ void __launch_bounds__(SEARCH_SELECT_THREADS) hmpc_search_select_kern
     __shared__ int part_i[SEARCH_SELECT_THREADS / 64];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchTree t = search_tree(s, d.nfix, k);
-    int cnt = 0;
+    int cnt = 0, open = 0;
     if (search_running(*t.state)) { // (the same in every thread)
         const int n = *t.n;
         const double ub = *t.ub;
+        // the rule's key takes the bound's place (best-first: it IS the bound); under a budget the tree stages `limit` picks, and
+        // with none left it still looks for ONE candidate, which it does not pick: search_select_anytime
+        const int order = search_tree_rule(s.rule, *t.inc), limit = search_pick_limit(width, s.budget1, *t.solves);
+        const int probe = limit > 0 ? limit : 1;
         double plb = -INFINITY;
         int pi = -1;
-        while (cnt < width) {
+        while (cnt < probe) {
             double blb = 0.0;
             int bi = -1;
             for (int i = tid; i < n; i += SEARCH_SELECT_THREADS) {
-                const double l = t.lb[i];
-                if (search_candidate(t.alive[i], l, ub, tol) && search_take(blb, bi, l, i, plb, pi)) { blb = l; bi = i; }
+                const double b = t.lb[i], l = search_rule_key(order, b, i);
+                if (search_candidate(t.alive[i], b, ub, tol) && search_take(blb, bi, l, i, plb, pi)) { blb = l; bi = i; }
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
@@ -73,13 +79,56 @@ __global__ void __launch_bounds__(SEARCH_SELECT_THREADS) hmpc_search_select_kern
                 if (search_take(blb, bi, part_lb[w], part_i[w], plb, pi)) { blb = part_lb[w]; bi = part_i[w]; }
             __syncthreads(); // (the next round overwrites the partial minima)
             if (bi < 0) break; // (the same in every thread)
-            if (tid == 0) s.picks[(size_t)k * SEARCH_MAX_WIDTH + cnt] = bi;
+            if (tid == 0 && cnt < limit) s.picks[(size_t)k * SEARCH_MAX_WIDTH + cnt] = bi;
             plb = blb;
             pi = bi;
             cnt++;
         }
+        open = cnt > limit; // (only with limit == 0: a candidate and no budget)
+        cnt = cnt < limit ? cnt : limit;
     }
-    if (tid == 0) s.count[k] = cnt;
+    if (tid == 0) {
+        s.count[k] = cnt;
+        if (s.open) s.open[k] = open;
+    }
+}
+
+// hmpc_search_set_budget: the trees a budget had stopped run again
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_reopen_kernel(const SearchState s)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < s.K; k += gridDim.x * blockDim.x)
+        if (search_budget_stopped(s.state[k])) s.state[k] = 0;
+}
+
+// hmpc_search_bounds: one wavefront per tree, the minimum of its leaves' bounds and the number of its candidates by shuffles
+// (a minimum is exact: the result does not depend on the order of the reduction)
+__global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_bounds_kernel(const BranchDims d, const SearchState s, const double tol, double *lower, double *upper,
+                                                                               int32_t *open)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = blockIdx.x * SEARCH_WAVES + wave; k < s.K; k += gridDim.x * SEARCH_WAVES) {
+        const SearchTree t = search_tree(s, d.nfix, k);
+        const int n = *t.n;
+        const double ub = *t.ub;
+        double lo = INFINITY;
+        int32_t cand = 0;
+        for (int i = lane; i < n; i += 64) {
+            const uint8_t a = t.alive[i];
+            const double l = t.lb[i];
+            if (a) lo = search_bound_min(lo, l);
+            cand += search_candidate(a, l, ub, tol);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = search_bound_min(lo, __shfl_xor(lo, o));
+            cand += __shfl_xor(cand, o);
+        }
+        if (lane == 0) {
+            lower[k] = search_bound_min(lo, *t.unc_lb);
+            upper[k] = ub;
+            open[k] = cand;
+        }
+    }
 }
 
 // Exclusive scan of v over the SEARCH_SCAN_CHUNK threads of the workgroup, in thread order; chunk: the sum over all of them.
@@ -176,7 +225,7 @@ __global__ void __launch_bounds__(64 * SEARCH_WAVES) hmpc_search_stage_kernel(co
     for (long long w = (long long)blockIdx.x * SEARCH_WAVES + wave; w < slots; w += (long long)gridDim.x * SEARCH_WAVES) {
         const int q = (int)(w % most), j = (int)((w / most) % width), k = (int)(w / most / width);
         const int cnt = s.count[k];
-        if (q == 0 && j == 0 && cnt == 0 && lane == 0 && search_running(s.state[k])) s.state[k] = search_done_word(s.inc[k]);
+        if (q == 0 && j == 0 && cnt == 0 && lane == 0 && search_running(s.state[k])) s.state[k] = search_stop_word(s.inc[k], s.open ? s.open[k] : 0);
         if (j >= cnt) continue; // (the same in every lane)
         const int lev = s.plev[(size_t)k * SEARCH_MAX_WIDTH + j];
         if (q >= search_pick_rows(lev)) continue; // the pick's record waits, or its block is shorter
@@ -525,6 +574,11 @@ struct hmpc_search {
     PinBuf<double> a_hval;                    // e0 | x0_next on their way up
     PinBuf<int32_t> a_hidx;                   // word (4) | cover | reopened on their way down
     DevBuf<int32_t> srow, sleft, plev, pfirst; // speculation: the waiting records of the nodes, the blocks of the staged picks
+    // anytime searches (include/hmpc_search_anytime.h): the trees a round found out of budget; the outputs of hmpc_search_bounds
+    DevBuf<int32_t> open, bd_open;
+    DevBuf<double> bd_val;                    // lower | upper
+    PinBuf<int32_t> h_bd_open;
+    PinBuf<double> h_bd_val;
     int32_t row0 = 0;      // first pool row of the staged (or next) round
     int32_t staged = 0;    // rows of the staged round (with waiting records a staged round may have none)
     int32_t staged_picks = 0, staged_waiting = 0; // its picks, 0: no round is staged / those of them whose record waits
@@ -600,11 +654,17 @@ extern "C" int hmpc_search_create(hmpc_handle *h, int32_t K, int32_t node_cap, i
     HIPCHK(s->sleft.alloc(nodes));
     HIPCHK(s->plev.alloc(k * SEARCH_MAX_WIDTH));
     HIPCHK(s->pfirst.alloc(k * SEARCH_MAX_WIDTH));
+    HIPCHK(s->open.alloc(k));
+    HIPCHK(s->bd_open.alloc(k));
+    HIPCHK(s->bd_val.alloc(2 * k));
+    HIPCHK(s->h_bd_open.alloc(k));
+    HIPCHK(s->h_bd_val.alloc(2 * k));
+    HIPCHK(hipMemset(s->open, 0, k * sizeof(int32_t)));
     int32_t *ti = s->ti;
     double *td = s->td;
     s->v = SearchState{K, node_cap, row_cap, s->fix, s->lb, s->row, s->wrow, s->alive, ti, ti + k, ti + 2 * k, ti + 3 * k, ti + 4 * k, ti + 5 * k,
                        td, td + k, s->x0, s->p_obj, s->p_dual_obj, s->p_status, s->p_iters, s->p_primal, s->p_dual, s->picks, s->count, s->offset, s->word,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, s->srow, s->sleft, s->plev, s->pfirst, 0};
+                       nullptr, nullptr, nullptr, nullptr, nullptr, s->srow, s->sleft, s->plev, s->pfirst, 0, HMPC_RULE_BEST_FIRST, 0, s->open};
     HIPCHK(search_alloc_batch(s.get(), batch));
     *out = s.release();
     return HMPC_OK;
@@ -1079,5 +1139,54 @@ extern "C" int hmpc_search_rows(hmpc_search *s, int32_t first, int32_t count, co
     HIPCHK(move(host->iters, v.p_iters + r, n * sizeof(int32_t)));
     HIPCHK(move(host->primal, v.p_primal + r * d.n_primal, n * d.n_primal * sizeof(double)));
     HIPCHK(move(host->dual, v.p_dual + r * d.n_dual, n * d.n_dual * sizeof(double)));
+    return HMPC_OK;
+}
+
+// ---- anytime searches: the entries of include/hmpc_search_anytime.h (arithmetic: hmpc_search.h) ---------------------------------
+extern "C" int hmpc_search_set_rule(hmpc_search *s, int32_t rule)
+{
+    g_err.clear();
+    if (rule < HMPC_RULE_BEST_FIRST || rule > HMPC_RULE_DIVE_THEN_BEST) return fail(HMPC_EINVAL, "search: the rule must lie in 0 .. 3 (HMPC_RULE_*)");
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    s->v.rule = rule;
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_set_budget(hmpc_search *s, int32_t max_solves, void *stream)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    // (stored as max_solves + 1, 0: none; a tree never consumes 2^31 - 1 picks, so the largest budget is as good as none)
+    s->v.budget1 = max_solves < 0 ? 0 : max_solves == INT32_MAX ? INT32_MAX : max_solves + 1;
+    if (!s->begun) return HMPC_OK; // (no tree has a state yet: begin writes them all)
+    HIPCHK(hipSetDevice(s->h->device));
+    const int threads = 64 * SEARCH_WAVES;
+    hipLaunchKernelGGL(hmpc_search_reopen_kernel, search_grid(((long long)s->v.K + 63) / 64), dim3(threads), 0, (hipStream_t)stream, s->v);
+    HIPCHK(hipGetLastError());
+    return HMPC_OK;
+}
+
+extern "C" int hmpc_search_bounds(hmpc_search *s, double tol, double *lower, double *upper, int32_t *open, void *stream)
+{
+    g_err.clear();
+    if (!s) return fail(HMPC_EINVAL, "search: null search");
+    if (!s->begun) return fail(HMPC_EINVAL, "search: no step has begun (hmpc_search_begin)");
+    if (s->staged_picks > 0) return fail(HMPC_EINVAL, "search: a round is staged (hmpc_search_consume comes first)");
+    if (!lower && !upper && !open) return HMPC_OK;
+    HIPCHK(hipSetDevice(s->h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t K = (size_t)s->v.K;
+    double *val = s->bd_val, *h_val = s->h_bd_val;
+    int32_t *h_open = s->h_bd_open;
+    hipLaunchKernelGGL(hmpc_search_bounds_kernel, search_grid((long long)K), dim3(64 * SEARCH_WAVES), 0, st, s->d, s->v, tol, val, val + K, (int32_t *)s->bd_open);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_val, val, 2 * K * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_open, s->bd_open, K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // the one synchronisation of the call
+    if (lower) std::copy(h_val, h_val + K, lower);
+    if (upper) std::copy(h_val + K, h_val + 2 * K, upper);
+    if (open) std::copy(h_open, h_open + K, open);
     return HMPC_OK;
 }

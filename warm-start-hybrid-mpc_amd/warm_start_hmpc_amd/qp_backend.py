@@ -182,7 +182,10 @@ def load_library():
                            ('hmpc_search_get_batch', [vp, i32] + [vp] * 5), ('hmpc_search_tree', [vp, i32] + [vp] * 7),
                            ('hmpc_search_rows', [vp, i32, i32, ctypes.POINTER(_Result), i32]),
                            ('hmpc_search_set_speculation', [vp, i32]), ('hmpc_search_staged', [vp, _ip, _ip]),
-                           ('hmpc_search_counters', [vp, ctypes.POINTER(ctypes.c_int64)]), ('hmpc_search_tree_waiting', [vp, i32, vp, vp])):
+                           ('hmpc_search_counters', [vp, ctypes.POINTER(ctypes.c_int64)]), ('hmpc_search_tree_waiting', [vp, i32, vp, vp]),
+                           # include/hmpc_search_anytime.h
+                           ('hmpc_search_set_rule', [vp, i32]), ('hmpc_search_set_budget', [vp, i32, vp]),
+                           ('hmpc_search_bounds', [vp, ctypes.c_double, vp, vp, vp, vp])):
             getattr(lib, name).restype = ctypes.c_int
             getattr(lib, name).argtypes = args
         _lib = lib
@@ -203,6 +206,10 @@ EXPORTED_SEARCH_SYMBOLS = ('hmpc_search_create', 'hmpc_search_destroy', 'hmpc_se
                            'hmpc_search_advance', 'hmpc_search_rebase', 'hmpc_search_get_batch', 'hmpc_search_tree', 'hmpc_search_rows',
                            'hmpc_search_set_speculation', 'hmpc_search_staged', 'hmpc_search_counters', 'hmpc_search_tree_waiting')
 SEARCH_STATES = dict(done=0x1, incumbent=0x2, failed=0x4, overflow=0x8)
+# include/hmpc_search_anytime.h (a header of its own again: the two above name what include/hmpc_search.h declares, no more)
+EXPORTED_SEARCH_ANYTIME_SYMBOLS = ('hmpc_search_set_rule', 'hmpc_search_set_budget', 'hmpc_search_bounds')
+SEARCH_RULES = dict(best=0, depth=1, breadth=2, dive=3)
+SEARCH_STOP_STATES = dict(budget=0x10)
 
 
 def _problem_struct(problem):

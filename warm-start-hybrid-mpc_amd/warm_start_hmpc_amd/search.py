@@ -12,7 +12,11 @@ from time import perf_counter
 import numpy as np
 
 from .batched import NodeArrays
-from .qp_backend import SEARCH_STATES, _Result, _Warm
+from . import branch_and_bound as bb
+from .qp_backend import SEARCH_RULES, SEARCH_STATES, SEARCH_STOP_STATES, _Result, _Warm
+
+# the reference's candidate_selection functions (branch_and_bound.py) as rules of the device search
+_RULE_OF_SELECTION = {bb.best_first: 'best', bb.depth_first: 'depth', bb.breadth_first: 'breadth'}
 
 
 class SearchTooBig(RuntimeError):
@@ -30,9 +34,14 @@ class DeviceSearch(object):
                hand-down on the descendants are solved cold and results agree to the solver's tolerance only.  A step then needs
                up to 2^(s+1) - 1 pool rows per launched pick instead of one: the default ``row_cap`` stays, so give a larger
                one where ``SearchTooBig`` is raised.
+    rule     : 'best' (the default: smallest bound first), 'depth' (the newest candidate first), 'breadth' (the oldest first) or
+               'dive' (per tree depth-first until it has an incumbent, best-first from then on) -- ``set_rule``.
+    max_solves : None, or the nodes a tree may consume per step (``set_budget``).  A tree that runs out of it with candidates
+               left stops with the state ``SEARCH_STOP_STATES['budget']`` (and ``SEARCH_STATES['incumbent']`` with it if it has
+               one); ``bounds()`` says what it has proved, and ``advance`` takes it if it has an incumbent.
     """
 
-    def __init__(self, controller, K, node_cap=1024, row_cap=None, speculation=0):
+    def __init__(self, controller, K, node_cap=1024, row_cap=None, speculation=0, rule='best', max_solves=None):
         qp = controller.qp
         if not hasattr(qp, 'handle') or not hasattr(qp, 'lib'):
             raise RuntimeError('DeviceSearch needs the HIP backend (the product path has no CPU fallback).')
@@ -51,6 +60,11 @@ class DeviceSearch(object):
         self.speculation = 0
         if speculation:
             self.set_speculation(speculation)
+        self.rule, self.max_solves = 'best', None
+        if rule != 'best':
+            self.set_rule(rule)
+        if max_solves is not None:
+            self.set_budget(max_solves)
 
     def __del__(self):
         s = getattr(self, '_s', None)
@@ -70,6 +84,44 @@ class DeviceSearch(object):
             raise ValueError('hmpc_search_set_speculation failed: %s' % self.qp.lib.hmpc_last_error().decode())
         self._check(rc)
         self.speculation = int(depth)
+
+    def set_rule(self, rule):
+        """The order in which the rounds to come pick among a tree's candidates: a key of ``SEARCH_RULES`` (or its code, or one
+        of the three selection functions of ``branch_and_bound.py``); not while a round is staged.  It holds until it is changed."""
+        name = _RULE_OF_SELECTION.get(rule, rule) if callable(rule) else rule
+        if callable(name):
+            raise ValueError('no rule of the device search for the selection function %r.' % (rule,))
+        if not isinstance(name, str):
+            name = {v: k for k, v in SEARCH_RULES.items()}.get(name, name)
+        if name not in SEARCH_RULES:
+            raise ValueError('rule must be one of %s.' % ', '.join(sorted(SEARCH_RULES)))
+        rc = self.qp.lib.hmpc_search_set_rule(self._s, SEARCH_RULES[name])
+        if rc == -1:
+            raise ValueError('hmpc_search_set_rule failed: %s' % self.qp.lib.hmpc_last_error().decode())
+        self._check(rc)
+        self.rule = name
+
+    def set_budget(self, max_solves, stream=None):
+        """The nodes a tree may consume per step from here on (None or negative: no budget); trees that an earlier budget had
+        stopped run again, so ``set_budget(None)`` -> ``run`` finishes a cut-off search.  Not while a round is staged."""
+        m = -1 if max_solves is None or max_solves < 0 else int(max_solves)
+        rc = self.qp.lib.hmpc_search_set_budget(self._s, m, ctypes.c_void_p(stream))
+        if rc == -1:
+            raise ValueError('hmpc_search_set_budget failed: %s' % self.qp.lib.hmpc_last_error().decode())
+        self._check(rc)
+        self.max_solves = None if m < 0 else m
+
+    def bounds(self, tol=0., stream=None):
+        """What every tree proves as it stands: dict lower (min over its leaves' bounds and the bounds of leaves pruned on
+        uncertified records: a lower bound of the MIQP's cost; +inf without leaves, -inf for a root), upper (the incumbent's
+        cost, +inf without one), open (candidates left at ``tol``).  Not while a round is staged."""
+        out = dict(lower=np.empty(self.K), upper=np.empty(self.K), open=np.empty(self.K, dtype=np.int32))
+        rc = self.qp.lib.hmpc_search_bounds(self._s, float(tol), out['lower'].ctypes.data, out['upper'].ctypes.data, out['open'].ctypes.data,
+                                            ctypes.c_void_p(stream))
+        if rc == -1:
+            raise ValueError('hmpc_search_bounds failed: %s' % self.qp.lib.hmpc_last_error().decode())
+        self._check(rc)
+        return out
 
     def counters(self):
         """Since ``begin``: dict rounds, launches (rounds that launched QPs), rows (nodes launched), served (picks consumed
@@ -256,10 +308,14 @@ class DeviceSearch(object):
         return out
 
     # ------------------------------------------------------------------
-    def feedforward_many(self, x0s, warm_starts=None, frontier_width=8, tol=0., handdown=True):
+    def feedforward_many(self, x0s, warm_starts=None, frontier_width=8, tol=0., handdown=True, search_rule=None):
         """Solves K MIQPs; the list of dicts of ``BatchedMPC.feedforward_many`` (objective, ub, x, uc, leaves, solves, time,
-        rounds).  ``x`` holds the two states the search returns (x0 and the model's next state), rows 0 and 1."""
+        rounds).  ``x`` holds the two states the search returns (x0 and the model's next state), rows 0 and 1.
+        search_rule: None (the search's rule as it is set) or ``best_first`` / ``depth_first`` / ``breadth_first`` of
+        ``branch_and_bound.py`` -- the reference's ``candidate_selection`` -- which becomes the search's rule."""
         x0s = np.atleast_2d(np.asarray(x0s, dtype=np.float64))
+        if search_rule is not None:
+            self.set_rule(search_rule)
         tic = perf_counter()
         self.begin(x0s, warm_starts)
         rounds, _ = self.run(frontier_width, tol, handdown)
@@ -282,12 +338,16 @@ class DeviceSearch(object):
             out.append(d)
         return out
 
-    def _closed_loop_resident(self, x0s, n_steps, errors, frontier_width, tol, handdown):
+    def _closed_loop_resident(self, x0s, n_steps, errors, frontier_width, tol, handdown, anytime=False):
         """``closed_loop`` with the trees, the pool and the step boundary on the device: ``begin`` once, then per step ``run`` ->
-        ``results`` (K small rows) -> ``advance``.  A tree without an incumbent gets an empty cover and stays empty."""
+        ``results`` (K small rows) -> ``advance``.  A tree without an incumbent gets an empty cover and stays empty.
+        anytime: the step's proven lower bounds and which trees their budget stopped are recorded too (``bounds``); a tree
+        cut off with an incumbent advances like one that proved its optimum."""
         K = self.K
         stats = dict(nodes_ws=np.zeros((K, n_steps), np.int64), len_ws=np.zeros((K, n_steps), np.int64), reopened=np.zeros((K, n_steps), np.int64),
                      costs=np.full((K, n_steps), np.nan))
+        if anytime:
+            stats.update(lower=np.full((K, n_steps), np.nan), stopped=np.zeros((K, n_steps), bool))
         alive = np.ones(K, dtype=bool)
         tic = perf_counter()
         steps = 0
@@ -303,6 +363,9 @@ class DeviceSearch(object):
             if np.any(bad):
                 raise RuntimeError('%d trees outgrew node_cap = %d' % (int((bad != 0).sum()), self.node_cap))
             stats['nodes_ws'][alive, t] = r['solves'][alive]
+            if anytime:
+                stats['lower'][alive, t] = self.bounds(tol)['lower'][alive]
+                stats['stopped'][alive, t] = (r['state'][alive] & SEARCH_STOP_STATES['budget']) != 0
             alive &= np.isfinite(r['cost'])
             if not alive.any():
                 break
@@ -366,7 +429,7 @@ class DeviceSearch(object):
         stats.update(steps=steps, wall=perf_counter() - tic)
         return stats
 
-    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True, resident=False, presolve=False):
+    def closed_loop(self, x0, n_steps, errors, frontier_width=8, tol=0., handdown=True, resident=False, presolve=False, rule=None, max_solves=None):
         """K closed loops from the same x0 (or from K states, (K, nx)) under prescribed model errors (K, n_steps, nx), as
         ``FleetMPC.closed_loop``: per step ``run``, then the leaves go through the backend's node shift (``hmpc_shift_batch``) and
         become the covers of ``begin``.  ``resident=True``: the same walk with the step boundary on the device (``advance``) -- no
@@ -377,17 +440,35 @@ class DeviceSearch(object):
         reopened, costs (NaN where a loop has ended), steps, wall.  With ``presolve`` also nodes_pre (solves of the idle-time run),
         nodes_rt and rounds_rt (n_steps: solves and rounds after the re-base -- what the controller waits for; step 0: the cold
         search), reopened_rt (leaves the re-base reopened), time_pre and time_rt (n_steps, seconds: advance + idle-time run /
-        re-base to results); nodes_ws is then nodes_pre + nodes_rt."""
+        re-base to results); nodes_ws is then nodes_pre + nodes_rt.
+        ``rule`` / ``max_solves`` (resident path only; either one given): the loop runs under that rule and with that budget of
+        solves per tree and step (``set_rule``, ``set_budget``; None: as the search is set), and the search has its own rule and
+        budget again when the loop returns.  A step whose tree its budget stopped
+        WITH an incumbent applies that incumbent's input and advances; one stopped without an incumbent ends its loop.  The dict
+        gains lower (K, n_steps: the proven lower bound of every step's MIQP, NaN where a loop has ended) and stopped (K, n_steps,
+        bool: the budget cut the step's search off)."""
         from .batched import BatchedMPC
         bm = BatchedMPC(self.c)                                 # (uploads the shift's maps)
         K = self.K
         errors = np.asarray(errors, dtype=np.float64)
         xs = np.asarray(x0, dtype=np.float64)
         xs = np.repeat(xs[None], K, axis=0) if xs.ndim == 1 else xs.copy()
+        anytime = rule is not None or max_solves is not None
+        if anytime and (presolve or not resident):
+            raise ValueError('rule and max_solves need resident=True (and no presolve).')
         if presolve:
             return self._closed_loop_presolve(xs, n_steps, errors, frontier_width, tol, handdown)
         if resident:
-            return self._closed_loop_resident(xs, n_steps, errors, frontier_width, tol, handdown)
+            was = (self.rule, self.max_solves)
+            try:
+                if rule is not None:
+                    self.set_rule(rule)
+                if max_solves is not None:
+                    self.set_budget(max_solves)
+                return self._closed_loop_resident(xs, n_steps, errors, frontier_width, tol, handdown, anytime)
+            finally:                                            # (the loop's rule and budget are the loop's: the search keeps its own)
+                self.set_rule(was[0])
+                self.set_budget(was[1])
         ws = None
         alive = np.ones(K, dtype=bool)
         nothing = NodeArrays(np.zeros((0, self.nfix), np.int8), np.zeros(0), np.zeros((0, self.n_dual)), np.zeros(0), np.zeros(0, bool))
