@@ -29,6 +29,9 @@ REF_FACTOR = 4.           # kernel and oracle sum the same rows in different ord
 
 
 
+EXTRA_LINES = []          # figures other test modules of a session want beside the parity margins: tests/test_gpu_parity.py writes them out with its own line
+
+
 def new_margins():
     """An accumulator a caller hands to assert_certified(margins=...): per class and residual [records' worst, reference's worst]
     over the calls that PASSED with a reference -- what test_gpu_parity writes into its line of parity margins."""

@@ -14,7 +14,9 @@ from helpers import random_mld, long_head_parts, _NoBackend
 
 # (nx, nuc, nub, seed, T): random MLDs of helpers.random_mld
 REGISTER_SHAPES = ((6, 2, 3, 3, 8), (6, 2, 3, 3, 12), (8, 3, 4, 2, 10), (8, 5, 2, 55, 12), (3, 3, 6, 38, 12),   # (the last two: the binaries round 4 saw come out wrong)
-                   (9, 3, 4, 23, 6), (8, 4, 4, 23, 6))   # nx + nu = 16: the full row of 16 lanes (round 4: every node NUMERICAL -- the LDS carve, fixed in round 5)
+                   (9, 3, 4, 23, 6), (8, 4, 4, 23, 6),   # nx + nu = 16: the full row of 16 lanes (round 4: every node NUMERICAL -- the LDS carve, fixed in round 5)
+                   (6, 2, 3, 3, 4), (4, 2, 1, 42, 12), (5, 2, 2, 21, 6),   # the 4096-leaf problems of tests/enumeration_reference.py (appended: tests/test_capi.py uses entry 0)
+                   (6, 2, 3, 3, 5))                                        # and its 32768-leaf one, which runs the compiled kernels once
 SIZED = ((20, 6, 8, 0, 30),       # BASELINE configs[4]: beyond one CU's LDS, the streaming form
          (10, 4, 4, 5, 8),        # nx + nu = 18: beyond the static row map, fits LDS (1 / 2 / 4 waves per node)
          (12, 3, 4, 23, 6))       # nx + nu = 19, another one

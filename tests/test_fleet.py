@@ -27,6 +27,13 @@ def test_fleet_walks_the_walk_of_the_numpy_driver():
     # so a node may be solved by the 1-, 2- or 4-wave kernel: last-digit differences in the multipliers)
     assert np.max(np.abs(fl['nodes_ws'] - np.array(py['nodes_ws']))) <= 6
     assert abs(fl['nodes_ws'][:, 1:].mean() - np.array(py['nodes_ws'])[:, 1:].mean()) < 0.5
+    # what the plant is given and where the model says it goes, every step of every loop (1e-5: the suite's parity tolerance,
+    # tests/test_gpu_parity.py RTOL; relative to the row's largest entry, floor 1e-2, as there)
+    for name in ('u0', 'x1'):
+        want = np.array(py[name])
+        assert want.shape == fl[name].shape == (K, steps, want.shape[2]) and not np.isnan(fl[name]).any(), name
+        scale = np.maximum(1e-2, np.max(np.abs(want), axis=2, keepdims=True))
+        assert np.max(np.abs(fl[name] - want) / scale) <= 1e-5, (name, np.max(np.abs(fl[name] - want) / scale))
 
 
 def test_fleet_replays_the_published_runs():

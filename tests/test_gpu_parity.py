@@ -15,7 +15,7 @@ import pytest
 from helpers import make_controller, load_fixture, random_prefix_frontier, random_mld, dive_leaf, dive_and_prefix_frontier, _NoBackend, exercise_bounded_qp
 from dense_qp import determined_inputs
 from kkt_checks import check_solution, is_disjoint_cover
-from certificates import assert_certified, record_from_device, new_margins, margins_line
+from certificates import assert_certified, record_from_device, new_margins, margins_line, EXTRA_LINES
 from warm_start_hmpc_amd.subproblem_solution import SubproblemSolution
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +64,7 @@ def _report_worst_deviations():
             'active-set solve %.2e; unpolished records (interior-point iterates) norm-wise %.2e'
             % (WORST['norm'], EFLOOR, WORST['element'], WORST['dense'], WORST['iterate']))
     line += '; ' + margins_line(MARGINS)
+    line = '\n'.join([line] + EXTRA_LINES)                  # (what modules that ran before this one left: tests/test_gpu_enumerated_miqp.py)
     print('\n' + line)
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     if os.path.isdir(out):

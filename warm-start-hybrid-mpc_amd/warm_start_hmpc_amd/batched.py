@@ -274,7 +274,8 @@ class BatchedMPC(object):
         random stream: the disturbances applied in the reference's published runs
         (``notebooks/cart_pole_with_walls/data/errors_sd_*.npy``) can be replayed step by step.
 
-        Returns dict: nodes_ws, nodes_cs (per sim, per step), len_ws, costs, alive steps, wall time, steps/s.
+        Returns dict: nodes_ws, nodes_cs (per sim, per step), len_ws, costs, u0, x1 (the applied input and the model's next
+        state, per sim and step with a solution), alive steps, wall time, steps/s.
         """
         K = len(seeds)
         rngs = [np.random.RandomState(s) for s in seeds]
@@ -283,7 +284,8 @@ class BatchedMPC(object):
         ws = [None] * K
         active = list(range(K))
         stats = dict(nodes_ws=[[] for _ in range(K)], nodes_cs=[[] for _ in range(K)], len_ws=[[] for _ in range(K)],
-                     costs=[[] for _ in range(K)], errors=[[] for _ in range(K)], reopened=[[] for _ in range(K)], cost_mismatches=[])
+                     costs=[[] for _ in range(K)], errors=[[] for _ in range(K)], reopened=[[] for _ in range(K)], cost_mismatches=[],
+                     u0=[[] for _ in range(K)], x1=[[] for _ in range(K)])
         tic = perf_counter()
         steps_done = 0
         for t in range(n_steps):
@@ -317,6 +319,8 @@ class BatchedMPC(object):
                 stats['reopened'][k].append(int((~ws[k].has_dual).sum()))   # infeasibility proofs lost in the shift
                 stats['costs'][k].append(r['objective'])
                 stats['errors'][k].append(e_t)
+                stats['u0'][k].append(np.concatenate((r['uc'][0], r['ub'][0])))
+                stats['x1'][k].append(r['x'][1].copy())
                 if log is not None:
                     cs = '(cs: {}, {:.3f}) '.format(cold[j]['solves'], cold[j]['time']) if cold is not None else ''
                     log.write('sim %d Time step %d %s(ws: %d, %.3f) (ws info: %d) (e: %.3f, %s)\n'

@@ -95,12 +95,14 @@ class FleetMPC(object):
     def closed_loop(self, x0, n_steps, errors, frontier_width=8, speculation=0, cold_speculation=0, cold_frontier_width=None):
         """K closed loops from the same x0 under prescribed model errors (K, n_steps, nx) -- the shape of
         ``BatchedMPC.closed_loop(errors=...)``.  Returns dict: costs, nodes_ws, len_ws, reopened (K, n_steps; NaN / 0
-        after a loop has ended), wall, wall_first_step (the cold start's share of it), steps, steps_per_sec."""
+        after a loop has ended), u0 (K, n_steps, nu) and x1 (K, n_steps, nx) -- the input every step applies and the model's next
+        state, NaN where a step has no solution --, wall, wall_first_step (the cold start's share of it), steps, steps_per_sec."""
         K = self.K
         errors = np.asarray(errors, dtype=np.float64)
         xs = np.repeat(np.asarray(x0, dtype=np.float64)[None], K, axis=0)
         st = dict(costs=np.full((K, n_steps), np.nan), nodes_ws=np.zeros((K, n_steps), dtype=np.int64),
-                  len_ws=np.zeros((K, n_steps), dtype=np.int64), reopened=np.zeros((K, n_steps), dtype=np.int64))
+                  len_ws=np.zeros((K, n_steps), dtype=np.int64), reopened=np.zeros((K, n_steps), dtype=np.int64),
+                  u0=np.full((K, n_steps, self.nu), np.nan), x1=np.full((K, n_steps, self.nx), np.nan))
         self.reset()
         steps = 0
         tic = perf_counter()
@@ -113,6 +115,7 @@ class FleetMPC(object):
             st['nodes_ws'][:, t] = r['solves']
             st['len_ws'][:, t] = cover
             st['reopened'][:, t] = reopened
+            st['u0'][ok, t], st['x1'][ok, t] = r['u0'][ok], r['x1'][ok]
             xs = np.where(ok[:, None], r['x1'] + errors[:, t], xs)
             steps += int(ok.sum())
             if t == 0:
