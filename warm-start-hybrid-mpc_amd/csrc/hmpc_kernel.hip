@@ -74,6 +74,12 @@
 #ifndef HMPC_NARROW_STAGE // (0: A/B builds in which a stage whose binaries are all fixed runs factor_reg's full-width body)
 #define HMPC_NARROW_STAGE 1
 #endif
+#ifndef HMPC_FACTOR_ROWS4 // (0: A/B builds in which lanes 0 .. nz-1 of factor_reg hold whole columns of the stage block)
+#define HMPC_FACTOR_ROWS4 1
+#endif
+#ifndef HMPC_ROWS4_XFER // the pivot row's way to the four rows of 16 lanes: 0 v_permlane32_swap + v_permlane16_swap, 1 ds_bpermute_b32
+#define HMPC_ROWS4_XFER 0
+#endif
 #define HMPC_POLISH_ATTEMPTS 3 // per solve: a node whose active set resists is left to the interior-point iterate
 #define HMPC_RETRY (-1) // internal: a hand-down attempt with the terminal-set rows did not verify, run the regular sequence
 #define HMPC_POLISH_ROUNDS_WARM 3 // active sets tried when the set is handed down by the parent node
@@ -204,9 +210,15 @@ DEV double bcast(double v, int src)
 // count of a broadcast, keeps the value in a VGPR (no VALU -> SGPR -> VALU hazard) and frees ~30 SGPRs that otherwise
 // spill.  Lanes of the other rows read lane src of THEIR row: they hold no component, their values are never read.
 // src must be a constant after unrolling (the DPP control is an immediate): the switch then folds to one case.
+DEV double bcast_row(double v, int src);
 template <class D> DEV double bcast16(double v, int src)
 {
     if constexpr (!D::kDpp) return bcast(v, src);
+    return bcast_row(v, src);
+}
+// The DPP form itself: EVERY row of 16 lanes reads lane src of its own row (factor_reg's stage block lies on all four rows).
+DEV double bcast_row(double v, int src)
+{
     const long x = __builtin_bit_cast(long, v);
     long r;
     switch (src) {
@@ -217,6 +229,30 @@ template <class D> DEV double bcast16(double v, int src)
     default: r = __builtin_amdgcn_update_dpp((long)0, x, 0x150 + 15, 0xf, 0xf, false); break;
     }
     return __builtin_bit_cast(double, r);
+}
+
+// Lane 16 r + c of every row r takes the value of lane 16 row + c (row: a constant after unrolling).  gfx950's row swaps stay in
+// the VALU: v_permlane32_swap of a value with itself leaves rows (0, 1, 0, 1) in one result and (2, 3, 2, 3) in the other,
+// v_permlane16_swap of the chosen one leaves its even row everywhere in one result and its odd row in the other -- four swaps and
+// their copies per double, against two ds_bpermute_b32 and their latency (HMPC_ROWS4_XFER=1) on every pivot of the chain.
+DEV unsigned bcast_rows32(unsigned x, int row, int lane)
+{
+#if HMPC_ROWS4_XFER == 1
+    return (unsigned)__builtin_amdgcn_ds_bpermute(((lane & 15) + 16 * row) * 4, (int)x);
+#else
+    // (as inline assembly: the register allocator of this compiler crashes on the two-result builtins in this kernel; the hazard
+    // recogniser does not look into assembly, so the two wait states between a VALU write and a swap that reads it are spelt out)
+    unsigned a, b, c, d;
+    asm("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %2\n\ts_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "=&v"(a), "=&v"(b) : "v"(x));
+    const unsigned y = row < 2 ? a : b;
+    asm("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %2\n\ts_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "=&v"(c), "=&v"(d) : "v"(y));
+    return (row & 1) ? d : c;
+#endif
+}
+DEV double bcast_rows(double v, int row, int lane)
+{
+    const unsigned lo = bcast_rows32((unsigned)__double2loint(v), row, lane), hi = bcast_rows32((unsigned)__double2hiint(v), row, lane);
+    return __hiloint2double((int)hi, (int)lo);
 }
 
 // Reciprocal to ~1 ulp: v_rcp_f64 (measured on MI355X: 4.5e-8 relative) and two Newton steps (2e-15, then
@@ -1453,6 +1489,10 @@ template <class D, int MQ> DEV int factor_tiles(const DevProb &p, const Lds &S, 
 //   * lane c < nz then owns column c of M = P + C' D C + W.  A pivot step broadcasts the pivot column
 //     with v_readlane and every lane updates its own column.  Fixed binaries are prescribed (identity
 //     row / column): their pivot steps are arithmetic no-ops, so the elimination needs no branch.
+// HMPC_FACTOR_ROWS4 (the default) lays the block of the third point over all four rows of 16 lanes instead: lane 16 r + c holds
+// the entries (i, c), i = r, r + 4, ..., so a stage forms, assembles and eliminates four block rows per instruction.  A pivot
+// step takes the pivot from its owner (v_readlane pair), the multipliers of a lane's rows from lane pj of its own row of lanes
+// (DPP) and the pivot row across the rows of lanes (bcast_rows); the first row of lanes stores the multipliers as before.
 // ---------------------------------------------------------------------------------------------
 template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane FSTAMP_ARGS)
 {
@@ -1510,6 +1550,21 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                 }
             }
         }
+#if HMPC_FACTOR_ROWS4
+        // The stage block on all four rows of 16 lanes: lane 16 r + c holds the entries (i, c) of the rows i = r, r + 4, r + 8, ... in
+        // col[k], k = i / 4 -- (nz + 3) / 4 registers instead of nz, and every instruction of a stage works on four block rows.
+        constexpr int NQ = (NZ + 3) / 4, NXQ = (NX + 3) / 4;
+        const int lr = lane >> 4, lc = lane & 15, lcc = lc < NZ ? lc : 0;
+        double ABc[NX], pn[NXQ];
+#pragma unroll
+        for (int l = 0; l < NX; l++) ABc[l] = lc < NZ ? S.AB[l * NZ + lcc] : 0.0;
+#pragma unroll
+        for (int k = 0; k < NXQ; k++) {
+            const int i = lr + 4 * k;
+            pn[k] = (i < NX && lc < NX) ? S.PT[(i < NX ? i : 0) * NX + (lc < NX ? lc : 0)] : 0.0;
+            if (i < NX && lc <= i) S.Pr[T * NXS + sym(i, lc)] = pn[k];
+        }
+#else
         double ABc[NX], pn[NX];
 #pragma unroll
         for (int l = 0; l < NX; l++) ABc[l] = lane < NZ ? S.AB[l * NZ + lane] : 0.0;
@@ -1520,6 +1575,7 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
             for (int i = 0; i < NX; i++)
                 if (i >= lane) S.Pr[T * NXS + sym(i, lane)] = pn[i];
         }
+#endif
         int bad = 0;
         for (int t = T - 1; t >= 0; t--) {
             const ldsi *fx = S.fix + t * NUB;
@@ -1579,6 +1635,118 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                     S.Mm[gj2 * NZ + gi2] = h0 + h1;
                 }
             }
+#if HMPC_FACTOR_ROWS4
+            // (2) y = P_{t+1} [A B](:, c) in every lane of column c.  P_{t+1}(i, l) is the entry (min, max) the previous stage left in
+            // lane 16 (min & 3) + max: a wave-uniform v_readlane pair.  (S.Pr holds the entries (max, min), which the elimination
+            // leaves different in the last bit: read from there, no record would keep its bits.)
+            double y[NX];
+#pragma unroll
+            for (int i = 0; i < NX; i++) {
+                double a = 0.0;
+#pragma unroll
+                for (int l = 0; l < NX; l++) {
+                    const int lo = l < i ? l : i, hi = l < i ? i : l;
+                    a += bcast(pn[lo >> 2], 16 * (lo & 3) + hi) * ABc[l];
+                }
+                y[i] = a;
+            }
+            double col[NQ], myrow[NU], dinv[NU];
+            int fm = 0, om = 0; // bit b: binary b of the stage is fixed / fixed to one (wave uniform)
+#pragma unroll
+            for (int b = 0; b < NUB; b++) {
+                const int v = __builtin_amdgcn_readfirstlane(fxv[b]);
+                fm |= (v >= 0) << b;
+                om |= (v == 1) << b;
+            }
+            // One body for the full block (NR = NZ) and for a stage whose binaries are ALL fixed by the node (NR = NX + NUC: rows and
+            // pivots of the binaries are prescribed, never formed): what either leaves in Lm, dinv, Pr and S.g is what the body with
+            // whole columns per lane leaves there, every entry through the same operations in the same order.
+            auto stage = [&](auto nr_) {
+                constexpr int NR = decltype(nr_)::value, NRQ = (NR + 3) / 4;
+                constexpr bool NARROW = NR < NZ;
+#pragma unroll
+                for (int k = 0; k < NRQ; k++) {
+                    const int i = lr + 4 * k, ic = i < NR ? i : 0;
+                    double a = 0.0;
+#pragma unroll
+                    for (int l = 0; l < NX; l++) a += S.AB[l * NZ + ic] * y[l];
+                    col[k] = a;
+                }
+                FSTAMP(0);
+                // (3) + P + C' D C (this wave wrote it: LDS operations of one wave complete in order); zero outside the block
+                const bool last = S.term_on && t == T - 1;
+#pragma unroll
+                for (int k = 0; k < NRQ; k++) {
+                    const int i = lr + 4 * k, ic = i < NR ? i : 0;
+                    const bool own = i < NR && lc < NZ;
+                    double a = col[k] + S.Mm[ic * NZ + lcc];
+                    if (last) a += TG[ic * NZ + lcc];
+                    col[k] = own ? a : 0.0;
+                }
+                FSTAMP(1);
+                // columns of binaries fixed to one (for the constant direction), before prescribing
+                if (NARROW ? om : fm) {
+                    double mbv[NRQ];
+#pragma unroll
+                    for (int k = 0; k < NRQ; k++) mbv[k] = 0.0;
+#pragma unroll
+                    for (int b = 0; b < NUB; b++)
+                        if ((om >> b) & 1) {
+#pragma unroll
+                            for (int k = 0; k < NRQ; k++) mbv[k] += bcast_row(col[k], NX + NUC + b);
+                        }
+                    if (lc == 0) {
+#pragma unroll
+                        for (int k = 0; k < NRQ; k++)
+                            if (lr + 4 * k < NR) S.g[t * NZ + lr + 4 * k] = mbv[k];
+                    }
+                    if (NARROW && lane >= NR && lane < NZ) S.g[t * NZ + lane] = 0.0; // (read by nothing: the sweeps override them)
+                } else if (lane < NZ) {
+                    S.g[t * NZ + lane] = 0.0;
+                }
+                if constexpr (NARROW) { // the binaries' columns: identity (their rows >= NR are never formed)
+#pragma unroll
+                    for (int k = 0; k < NRQ; k++) col[k] = lc >= NR ? 0.0 : col[k];
+                } else if (fm) {        // identity row and column at every fixed binary
+                    const int fz = fm << (NX + NUC);
+#pragma unroll
+                    for (int k = 0; k < NRQ; k++) {
+                        const int i = lr + 4 * k;
+                        col[k] = (((fz >> lc) | (fz >> i)) & 1) ? (i == lc ? 1.0 : 0.0) : col[k];
+                    }
+                }
+                FSTAMP(2);
+                // The multiplier of row i at pivot j is M(i, pj) / d; by symmetry the lanes of column i hold it as M(pj, i) / d once
+                // the pivot row has reached the four rows of lanes: lane i of the first row stores the multipliers of row i.
+                auto pivot = [&](const int j) {
+                    const int pj = NX + j;
+                    const double d = bcast(col[pj >> 2], 16 * (pj & 3) + pj); // 1 at a prescribed pivot: the step below changes nothing
+                    if (!(d > 0.0)) bad = 1;
+                    double rinv = __builtin_amdgcn_rcp(d);
+                    rinv = rinv * (2.0 - d * rinv);
+                    dinv[j] = rinv;
+                    const double cr = bcast_rows(col[pj >> 2] * rinv, pj & 3, lane);
+                    myrow[j] = (lane < NX || lane > pj) ? cr : 0.0;
+#pragma unroll
+                    for (int k = 0; k < NRQ; k++) { // (a register whose rows are all reduced already is left alone; single reduced
+                                                    // rows next to live ones take the step: nothing reads them again)
+                        if (4 * k < NX || 4 * k + 3 > pj) col[k] -= bcast_row(col[k], pj) * cr;
+                    }
+                };
+#pragma unroll
+                for (int j = 0; j < NUC; j++) pivot(j);
+                // a stage whose binaries are all fixed (most stages of a deep node): their pivot steps are no-ops
+                if (NARROW || ((S.fullfix >> t) & 1ull)) {
+#pragma unroll
+                    for (int j = NUC; j < NU; j++) { myrow[j] = 0.0; dinv[j] = 1.0; }
+                } else {
+#pragma unroll
+                    for (int j = NUC; j < NU; j++) pivot(j);
+                }
+            };
+            if (HMPC_NARROW_STAGE && NUB > 0 && __builtin_amdgcn_readfirstlane((int)((S.fullfix >> t) & 1ull))) stage(std::integral_constant<int, NX + NUC>());
+            else stage(std::integral_constant<int, NZ>());
+#else
             // (2) column `lane` of W = [A B]' P_{t+1} [A B]
             double y[NX];
 #pragma unroll
@@ -1737,6 +1905,7 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                   for (int j = NUC; j < NU; j++) pivot(j);
               }
             }
+#endif
             if (lane < NZ) { // rows of the states: NU entries; row i of the inputs: its i entries (zeros at skipped pivots)
                 ldsd *row = Lm + (lane < NX ? lane * NU : LM_U(NX, NU, lane - NX, 0));
 #pragma unroll
@@ -1750,6 +1919,14 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                 S.dinv[t * NU + lane] = dv;
             }
             FSTAMP(3);
+#if HMPC_FACTOR_ROWS4
+#pragma unroll
+            for (int k = 0; k < NXQ; k++) {
+                const int i = lr + 4 * k;
+                pn[k] = col[k];
+                if (i < NX && lc <= i) S.Pr[t * NXS + sym(i, lc)] = col[k];
+            }
+#else
 #pragma unroll
             for (int i = 0; i < NX; i++) pn[i] = col[i];
             if (lane < NX) {
@@ -1757,6 +1934,7 @@ template <class D> DEV int factor_reg(const DevProb &p, const Lds &S, int lane F
                 for (int i = 0; i < NX; i++)
                     if (i >= lane) S.Pr[t * NXS + sym(i, lane)] = col[i];
             }
+#endif
             FSTAMP(4);
         }
         if (lane == 0 && bad) S.flag[0] = 1;
@@ -3988,9 +4166,10 @@ hmpc_qp_kernel(const DevProb p_arg, const double *__restrict__ x0g, int x0_strid
     // (guard: a workgroup never takes more nodes than the launch has -- a binary whose node counter came out of the compiler wrong
     // has been seen to spin here for good, profiles/r05_compiler_bisect.md; with the guard it ends, loudly wrong)
     for (int slot = blockIdx.x, guard = 0; slot < Bn && guard <= Bn; guard++) {
-        // `order` (optional): the nodes sorted by the number of fixed binaries, shallow first -- shallow nodes take more
-        // iterations (correlation -0.5 .. -0.75 on random frontiers), and with ~4 nodes per workgroup handing out the
-        // long ones first shortens the tail of a launch
+        // `order` (optional): the nodes sorted by the number of fixed binaries, shallow first.  On RANDOM frontiers shallow nodes
+        // take more iterations (correlation -0.5 .. -0.75) and handing out the long ones first shortens the tail of a launch; on
+        // the frontiers of real trees the number of fixed binaries says next to nothing about the iteration count (+0.12 on the
+        // headline tree, +0.07 on distinct states): there the order neither helps nor hurts, and the tail stays
         int qp = order ? order[slot] : slot;
         if constexpr (WARM) { if (warm.second) qp = warm.pend[1 + slot]; }
         __syncthreads();
@@ -4146,6 +4325,7 @@ hmpc_qp_kernel(const DevProb p_arg, const double *__restrict__ x0g, int x0_strid
 #ifndef HMPC_KERNEL_ONLY // (the instance files and the code-generation probes compile hmpc_qp_kernel only)
 // Processing order of a large frontier: counting sort of the nodes by their number of fixed binaries (one workgroup;
 // the order inside a bucket is whatever the atomics give -- a record does not depend on when its node is solved).
+// Shallow first pays on random frontiers only; nothing known before a solve orders the nodes of a real tree.
 // Launches with hand-down (warm.index set): a node whose PARENT needed the terminal-set rows goes first -- its own solve is
 // the long kind (up to two full solves when the handed-down set does not verify, ~5.6 ms against ~2 ms), and a long node
 // that starts late is the tail of the launch (measured on real trees: 11.8 ms per 4096 nodes with such nodes scattered).
