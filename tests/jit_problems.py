@@ -24,6 +24,10 @@ SIZED = ((20, 6, 8, 0, 30),       # BASELINE configs[4]: beyond one CU's LDS, th
 
 # (fixture, T, terminal set): the controllers of tests/ and bench.py (helpers.make_controller)
 CONTROLLERS = tuple((f, T, term) for f in ('cart_pole_with_walls', 'cart_pole_one_wall') for T in (10, 20, 40) for term in (True, False))
+# (controller, HMPC_JIT_FLAGS): builds with other flags that a test runs -- cache entries of their own (the flags are part of the key).
+# The build without the paired solve: the control of tests/test_iterate_trajectory.py
+WITHOUT_PAIR = '-DHMPC_PAIR=0'
+FLAGGED = ((('cart_pole_with_walls', 10, True), WITHOUT_PAIR),)
 
 
 def problem(nx, nuc, nub, seed, T):
